@@ -13,19 +13,32 @@ stream of N x --bytes into rank shards (patternmatching_amd.shard.shard_plan:
 each rank generates its shard plus the max_len-1 bytes before it as
 context), so the all-reduced match count is that of the whole stream.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: start-up, the
+warmups, the K timed steps, and one JSON line (value, ms_per_step, the
+kernel time of the timed steps and the roofline fraction it gives).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step
+handed its caller, as .npy files (see dump_outputs).  The inputs are seeded:
+the same arguments give the same stream, so two builds compare output for
+output.
+
+--full adds everything else the benchmark measures: the CPU-baseline legs
+(before anything touches a GPU), after the timed steps the all-matches count
+and the per-pattern histogram, the live streaming floor of the RT kernel,
+and, for the default workload (snort, ascii, dense, rt), `count_only` (the
+same stream, the RT kernel counting matches, no ids written), `deep` (the
+lines stream -- the dictionary's own patterns back to back -- through the
+`auto` kind, with the reference CPU loop timed on a sample of it) and
+`configs` (the other BASELINE.json configurations).  --no-cpu and --no-extra
+trim a --full run.
 
 With --gpus N > 1 and no launcher (no WORLD_SIZE in the environment) the
 process starts N ranks itself (one child process per GPU, rendezvous on
-127.0.0.1) after running the CPU-baseline leg, before anything touches a
-GPU.  Under a launcher WORLD_SIZE must equal --gpus.
-
-The default run (snort, ascii, dense, rt) adds, after the timed steps, two
-more measurements to the same JSON line: `count_only` (the same stream, the
-RT kernel counting matches, no ids written) and `deep` (the lines stream --
-the dictionary's own patterns back to back -- through the `auto` kind, with
-the reference CPU loop timed on a sample of it).
+127.0.0.1), with --full after running the CPU-baseline leg, before anything
+touches a GPU.  Under a launcher WORLD_SIZE must equal --gpus.
 
 Prints one JSON line on rank 0.
 """
@@ -76,8 +89,16 @@ def parse(argv=None):
     p.add_argument("--cpu-sample", type=int, default=256 << 20, help="bytes of the CPU-baseline sample")
     p.add_argument("--cpu-cores", type=int, default=0,
                    help="CPU-baseline processes (0 = the job's host-core share, bounded by memory)")
-    p.add_argument("--no-cpu", action="store_true")
-    p.add_argument("--no-extra", action="store_true", help="skip the count_only and deep measurements")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline: the CPU baselines, the all-matches count and "
+                        "per-pattern histogram, the streaming floor, and for the default workload count_only, deep "
+                        "and the other BASELINE.json configs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step handed its caller to DIR/<name>.npy "
+                        "(float32 / float64, at most 64 MB: a fixed seeded sample of a larger output)")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    p.add_argument("--no-extra", action="store_true",
+                   help="with --full: skip the count_only, deep and other-config measurements")
     p.add_argument("--image-cache", default="auto",
                    help="compiled-automaton cache directory (SURVEY §8f item 2): 'auto' = $PM_IMAGE_CACHE, or with "
                         "more than one rank /tmp/pm_image_cache (rank 0 compiles and writes it, the other ranks "
@@ -219,7 +240,7 @@ def compile_ordered(build, cache_dir, use_dist, rank, dist):
 
 
 def extras_on(args):
-    return (not args.no_extra and args.stream == "ascii" and args.mode == "dense" and args.kernel == "rt"
+    return (args.full and not args.no_extra and args.stream == "ascii" and args.mode == "dense" and args.kernel == "rt"
             and args.layout == "shards")
 
 
@@ -237,13 +258,13 @@ def free_port():
 
 def launch_ranks(args):
     """Start args.gpus ranks (this script, one child process per GPU) with
-    the torch.distributed environment a launcher would set.  The CPU leg runs
-    here first, before any process touches a GPU, and reaches rank 0 through
+    the torch.distributed environment a launcher would set.  The CPU leg
+    (--full) runs here first, before any process touches a GPU, and reaches rank 0 through
     a file.  Returns the exit status (the first failing rank's)."""
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cpu_path = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         with tempfile.NamedTemporaryFile("w", prefix="pm_bench_cpu_", suffix=".json", dir="/tmp", delete=False) as f:
             json.dump(cpu_legs(args), f)
             cpu_path = f.name
@@ -293,9 +314,9 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
 
-    # CPU legs first, before this process touches the GPU (every N)
+    # CPU legs first, before this process touches the GPU (every N; --full)
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         path = os.environ.get("PM_BENCH_CPU_JSON")
         if path:
             with open(path) as f:
@@ -510,12 +531,15 @@ def main():
     torch.cuda.synchronize()
     count_ar_ms = (time.perf_counter() - t_cnt) * 1e3
 
-    # after the timed region: all-matches (patterns ending at each position,
-    # i.e. the suffix-chain length of each id), the per-pattern histogram
-    # (all-reduced: SURVEY §8e) and, with --score, accuracy against the
-    # reliable AC instance, all on the device
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, count, rank, world)
+
+    # after the timed region (--full, or --score): all-matches (patterns
+    # ending at each position, i.e. the suffix-chain length of each id), the
+    # per-pattern histogram (all-reduced: SURVEY §8e) and, with --score,
+    # accuracy against the reliable AC instance, all on the device
     extra = {}
-    if width == 4:
+    if width == 4 and (args.full or args.score):
         sc = torch.zeros(5, dtype=torch.int64, device="cuda")
         m.score_device(out.data_ptr(), out.data_ptr(), n, sc.data_ptr(), stream.cuda_stream)
         allm = sc.clone()
@@ -562,9 +586,9 @@ def main():
 
     # the same kernel's streaming floor, live on this GPU: rt_scan_kernel<2>
     # runs the chunk loop's loads and stores with no lookups (its ids are
-    # not matches; `out` is not used after this)
+    # not matches; `out` is not used after this).  --full only
     floor = None
-    if rank == 0 and args.kernel == "rt" and pos0 == 0:
+    if args.full and rank == 0 and args.kernel == "rt" and pos0 == 0:
         fts = []
         for r in range(4):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -648,6 +672,8 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "full": args.full,
+            "outputs_dir": args.dump_outputs,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -705,6 +731,44 @@ def main():
         print(json.dumps(res), flush=True)
     if use_dist:
         dist.destroy_process_group()
+
+
+DUMP_WHOLE = 8 << 20   # outputs up to this many positions are written whole (float32: 32 MiB)
+DUMP_EDGE = 1 << 20    # of a larger output: its first and last positions ...
+DUMP_SAMPLE = 4 << 20  # ... and this many positions between, drawn with a fixed seed
+
+
+def dump_outputs(dirpath, out, count, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as
+    DIR/<name>.npy (with more than one rank, <name>_rank<r>.npy).
+
+    match_ids (float32; dense and dense16 modes): the id the step wrote for
+    each stream position, 0 = no match.  Ids are 1..n_patterns, far below
+    2^24, so float32 holds them exactly.  An output of more than DUMP_WHOLE
+    positions is sampled: its first and last DUMP_EDGE positions and, between
+    them, DUMP_SAMPLE positions drawn once with a fixed seed (torch's CPU
+    generator, seed 0; the same positions for the same --bytes), in stream
+    order -- 24 MiB.
+    match_count (float64, one element): the caller's match counter after the
+    last timed step.  The counter accumulates over the timed steps, so this
+    is --steps times one step's count."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    if out is not None:
+        n = out.numel()
+        if n <= DUMP_WHOLE:
+            ids = out
+        else:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            mid = torch.randint(DUMP_EDGE, n - DUMP_EDGE, (DUMP_SAMPLE,), generator=g, dtype=torch.int64).sort().values
+            idx = torch.cat([torch.arange(DUMP_EDGE), mid, torch.arange(n - DUMP_EDGE, n)])
+            ids = out[idx.to(out.device)]
+        ids = ids.cpu().numpy()
+        ids = ids.view(np.uint16 if ids.dtype == np.int16 else np.uint32)  # the kernel writes unsigned ids
+        np.save(os.path.join(dirpath, f"match_ids{suffix}.npy"), ids.astype(np.float32))
+    np.save(os.path.join(dirpath, f"match_count{suffix}.npy"), count.cpu().numpy().astype(np.float64))
 
 
 def other_configs(args, pm, lib, world, all_reduce, dist, text, out):

@@ -13,7 +13,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -q -rf ${PYTEST_ARGS:-} > "$OUT/
 rc=$?; tail -5 "$OUT/pytest_gpu_$TAG.log"; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python __graft_entry__.py smoke > "$OUT/smoke_$TAG.log" 2>&1 || exit $?
 cat "$OUT/smoke_$TAG.log"
-timeout -k 10 600 python bench.py > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err" || { tail "$OUT/bench_$TAG.err"; exit 1; }
+timeout -k 10 600 python bench.py --full >"$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err" || { tail "$OUT/bench_$TAG.err"; exit 1; }
 cat "$OUT/bench_$TAG.json"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG" -o bench -- \

@@ -67,7 +67,7 @@ def test_gpus_flag_starts_that_many_ranks_without_a_launcher():
     rendezvous + collectives rehearsed on gloo without a GPU); the CPU leg
     runs first and reaches rank 0's line at N = 2."""
     r = _rehearse(["--gpus", "2", "--dict", "et", "--cpu-sample", str(1 << 20), "--cpu-cores", "2",
-                   "--no-extra"])
+                   "--no-extra", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -76,6 +76,17 @@ def test_gpus_flag_starts_that_many_ranks_without_a_launcher():
     assert d["rank_sum"] == 3.0 and sorted(x["rank"] for x in d["per_rank"]) == [0, 1]
     assert len({x["pid"] for x in d["per_rank"]}) == 2
     assert d["cpu_baseline"]["value"] > 0
+
+
+def test_plain_run_leaves_the_cpu_baseline_to_full():
+    """Without --full no CPU leg runs, whatever --no-cpu says."""
+    r = _rehearse(["--gpus", "2", "--dict", "et", "--cpu-sample", str(1 << 20), "--cpu-cores", "2",
+                   "--image-cache", "off"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["rehearsal"] and d["n_gpus"] == 2 and d["cpu_baseline"] is None
 
 
 def test_eight_rank_rehearsal_shares_one_compile(tmp_path):
@@ -149,6 +160,66 @@ def test_bench_json_line_contract():
     assert abs(r["achieved"] - (16 << 20) * 5 / (d["kernel_ms"] * 1e-3) / 1e9) / r["achieved"] < 0.01
     assert abs(d["value"] - (16 << 20) / (d["ms_per_step"] * 1e-3) / 1e9) / d["value"] < 0.02
     assert d["matches_per_step"] > 0.8 * (16 << 20)  # snort on ASCII: ~92 % non-null
+    # a plain run: the headline only, everything else waits for --full
+    assert d["full"] is False and d["roofline"]["streaming_floor"] is None
+    for k in ("count_only", "deep", "configs", "pattern_counts", "all_matches_per_step"):
+        assert k not in d, k
+
+
+def _dump(out, extra):
+    import numpy as np
+    d = _run(["--dict", "et", "--dump-outputs", str(out)] + extra)
+    arrays = {p.name[:-4]: np.load(p) for p in sorted(out.iterdir())}
+    assert sum(a.nbytes for a in arrays.values()) <= 64_000_000
+    return d, arrays
+
+
+@pytest.fixture(scope="module")
+def small_dump(tmp_path_factory):
+    """One run over 1 MiB of the seed-1 ASCII stream (et.dict), outputs dumped."""
+    return _dump(tmp_path_factory.mktemp("dump") / "small", ["--bytes", str(1 << 20)])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_whole_and_repeatable(small_dump, tmp_path):
+    """--dump-outputs: a 1 MiB output is written whole as float32, the ids'
+    non-null count is the step's match count, the counter holds --steps
+    steps, and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    n = 1 << 20
+    d, a = small_dump
+    assert sorted(a) == ["match_count", "match_ids"]
+    assert a["match_ids"].dtype == np.float32 and a["match_ids"].shape == (n,)
+    assert a["match_count"].dtype == np.float64 and a["match_count"].shape == (1,)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["outputs_dir"].endswith("small")
+    assert np.count_nonzero(a["match_ids"]) == d["matches_per_step"] > 0
+    assert a["match_count"][0] == 2 * d["matches_per_step"]
+    assert a["match_ids"].min() == 0 and a["match_ids"].max() == np.floor(a["match_ids"].max()) >= 1
+    _, b = _dump(tmp_path / "again", ["--bytes", str(n)])
+    assert np.array_equal(a["match_ids"], b["match_ids"]) and np.array_equal(a["match_count"], b["match_count"])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_samples_a_large_output(small_dump, tmp_path):
+    """An output above 8 Mi positions is sampled: the first and last 1 Mi
+    positions whole, 4 Mi seeded positions between.  The head equals the
+    whole dump of a run over the first 1 MiB alone: the stream is seeded, and
+    a position's id depends on the bytes up to it only."""
+    import numpy as np
+    d, a = _dump(tmp_path / "big", [])  # 16 MiB
+    ids = a["match_ids"]
+    assert ids.dtype == np.float32 and ids.shape == (6 << 20,)
+    assert np.array_equal(ids[: 1 << 20], small_dump[1]["match_ids"])
+    # 6 Mi of 16 Mi positions: the sample's match fraction is the stream's
+    frac = np.count_nonzero(ids) / ids.size
+    assert abs(frac - d["matches_per_step"] / (16 << 20)) < 0.01
+    assert a["match_count"][0] == 2 * d["matches_per_step"]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_count_mode_writes_the_counter_only(tmp_path):
+    d, c = _dump(tmp_path / "count", ["--mode", "count", "--bytes", str(1 << 20)])
+    assert sorted(c) == ["match_count"] and c["match_count"][0] == 2 * d["matches_per_step"] > 0
 
 
 @pytest.mark.gpu
@@ -218,10 +289,10 @@ def test_bench_gpus_two_self_launched_sums_two_single_runs():
 
 @pytest.mark.gpu
 def test_bench_default_extras():
-    """The default run's count_only and deep objects (small sizes): the deep
+    """The default workload's --full run: count_only and deep objects (small sizes): the deep
     lines stream through the auto kind picks a DFA form, count-only counts
     the same matches as the dense run."""
-    d = _run([])
+    d = _run(["--full"])
     c = d["count_only"]
     assert c["matches_per_step"] == d["matches_per_step"] and c["roofline"]["frac"] > 0
     deep = d["deep"]
