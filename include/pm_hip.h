@@ -91,6 +91,57 @@ int pm_hip_scan_device(void* obj, const uint8_t* d_text, int64_t stream_start, i
 int pm_hip_scan_device16(void* obj, const uint8_t* d_text, int64_t stream_start, int64_t pos0,
                          int64_t n, uint16_t* d_out, unsigned long long* d_count, void* hip_stream);
 
+/*
+ * Batched scan: nseg independent streams (packets, flows, small files, log
+ * lines) in one launch.  The streams lie back to back in one buffer of n
+ * bytes; offsets has nseg + 1 non-decreasing int64 values with offsets[0] ==
+ * 0 and offsets[nseg] == n, and stream j is bytes [offsets[j], offsets[j+1]).
+ * Empty streams, and runs of them, are legal.  The answer at position i of
+ * stream j is what read_char returns after reset() and the stream's bytes up
+ * to and including i (mpac.c:304-319 from the root state): the reset at a new
+ * stream file of the reference's loop (measure.c:241-311), once per stream
+ * inside one call.  Output is dense, n ids in buffer order: stream j's
+ * answers are d_out[offsets[j] .. offsets[j+1]).
+ *   d_text      device buffer, 16-byte aligned, n bytes.
+ *   d_offsets   DEVICE pointer, 8-byte aligned, nseg + 1 values.  The device
+ *               form does not check them: offsets that are not sorted, or do
+ *               not end at n, give unspecified ids, but never a read outside
+ *               d_text[0, round_up(n, 16)) or a write outside d_out[0, n).
+ *   d_out       n u32 gids (16-byte aligned), or NULL for count only.
+ *   d_count     device u64 += non-null positions (may be NULL).
+ * Asynchronous, on hip_stream; needs no scratch and allocates nothing, so it
+ * may be captured into a graph without pm_hip_prepare_capture.  Like
+ * pm_hip_scan_device it asks the resident read_block server to leave the
+ * device first.  nseg == 0 or n == 0: returns 0, launches nothing.
+ * Returns 0, -1 before compile(), -2 bad arguments (negative nseg or n,
+ * alignment), -3 launch error, and
+ *   -6  the object holds no reverse-trie image: the ac kind, and an rt / auto
+ *       object whose dictionary compile() gave to the DFA because the
+ *       reverse-trie encoding did not hold it.  The batched scan is the
+ *       reverse-trie walk with a stream start per position; a segmented DFA
+ *       walk is out of scope.  Nothing is launched, d_out is untouched and
+ *       pm_hip_last_error says why.
+ * Launches of at most "rt_small_max" positions run one thread per position
+ * over the global tables, larger ones one workgroup per CU (DESIGN.md §4,
+ * rt_batch_kernel).
+ */
+int pm_hip_scan_batch_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                             int64_t n, uint32_t* d_out, unsigned long long* d_count, void* hip_stream);
+/* The same with u16 gids; -4 above 65,535 patterns, as pm_hip_scan_device16. */
+int pm_hip_scan_batch_device16(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                               int64_t n, uint16_t* d_out, unsigned long long* d_count, void* hip_stream);
+/* Host forms: buf holds the streams back to back, offsets is a HOST array of
+ * nseg + 1 values, checked here (offsets[0] == 0, non-decreasing: else -2);
+ * n = offsets[nseg].  Text and offsets are copied to device staging the
+ * object keeps (counted in pm_hip_scratch_bytes; plain copies from pageable
+ * memory, not read_block's pinned pool), one batch launch, the ids copied
+ * back, one synchronize.  out_gid: n u32 gids; pm_hip_read_batch maps them to
+ * the add_pattern ids as pm_hip_read_block does.  They neither read nor
+ * change what read_block / read_char carry across calls: a batch call in the
+ * middle of a stream is invisible to that stream.  Codes as above (-6 too). */
+int pm_hip_read_batch_gid(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* out_gid);
+int pm_hip_read_batch(void* obj, const char* buf, const int64_t* offsets, size_t nseg, pm_pattern_id_t* out);
+
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,
  * PatternsTree.c:485-494): per position, equal -> success; d_algo's pattern

@@ -11,17 +11,20 @@ interface:
     HipMatcher      one MpsElem instance (create / add_pattern / compile /
                     read_char / read_block / reset / total_mem / free)
     gen_stream      the synthetic stream specification
+    batch_offsets   the offsets array of a list of streams, for the batched
+                    scan (HipMatcher.read_batch_* / scan_batch_device)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401
     Dictionary,
     HipMatcher,
     gen_stream,
+    batch_offsets,
     parse_line,
     KIND_RT,
     KIND_AC,
     KIND_AUTO,
 )
 
-__all__ = ["load", "Dictionary", "HipMatcher", "gen_stream", "parse_line", "KIND_RT", "KIND_AC", "KIND_AUTO",
-           "LIB_PATH", "CLI_PATH"]
+__all__ = ["load", "Dictionary", "HipMatcher", "gen_stream", "batch_offsets", "parse_line", "KIND_RT", "KIND_AC",
+           "KIND_AUTO", "LIB_PATH", "CLI_PATH"]

@@ -87,6 +87,13 @@ SIGNATURES = {
                                           c_vp, c_vp]),
     "pm_hip_scan_device16": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_vp,
                                             c_vp, c_vp]),
+    "pm_hip_scan_batch_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp,
+                                                c_vp]),
+    "pm_hip_scan_batch_device16": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp,
+                                                  c_vp]),
+    "pm_hip_read_batch_gid": (ctypes.c_int, [c_vp, c_u8p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, c_u32p]),
+    "pm_hip_read_batch": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t,
+                                         ctypes.POINTER(c_vp)]),
     "pm_hip_score_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),
     "pm_hip_parent_gid": (ctypes.c_uint32, [c_vp, ctypes.c_uint32]),
     "pm_hip_set_image_cache": (None, [c_vp, ctypes.c_char_p]),

@@ -88,6 +88,15 @@ struct DfaDev {
 // gids, valid when every gid < 65536), or null; count (u64) may be null.
 hipError_t pm_launch_rt(const uint8_t* text, int64_t stream_start, int64_t pos0, int64_t n, void* out, int outw,
                         unsigned long long* count, const RtDev& t, int num_cu, hipStream_t s);
+// Batched scan: nseg independent streams back to back in text[0, n), stream
+// j = bytes [offsets[j], offsets[j+1]) (nseg + 1 non-decreasing device int64
+// values, offsets[0] = 0, offsets[nseg] = n; empty streams are legal).
+// out[i] answers position i of the stream holding it, from that stream's
+// first byte (rt_batch_kernel).  out / outw / count as pm_launch_rt.  Needs
+// no scratch and allocates nothing.  Whatever offsets holds, reads stay in
+// text[0, n) and offsets[0, nseg], writes in out[0, n).
+hipError_t pm_launch_rt_batch(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n, void* out,
+                              int outw, unsigned long long* count, const RtDev& t, int num_cu, hipStream_t s);
 // The RT kernel's streaming floor (rt_scan_kernel<2>: the chunk loop's loads
 // and stores, no lookups; its ids are not matches) over text[0, n).
 hipError_t pm_launch_rt_floor(const uint8_t* text, int64_t n, void* out, int outw, const RtDev& t, int num_cu,

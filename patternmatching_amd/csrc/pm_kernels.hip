@@ -1338,6 +1338,126 @@ __global__ __launch_bounds__(RT_SERVE_THREADS) void rt_serve_kernel(PmServeReq* 
     }
 }
 
+// ---- batched scan: many independent streams in one launch ------------------
+// nseg streams lie back to back in text[0, n): stream j is bytes
+// [offs[j], offs[j+1]), offs has nseg + 1 non-decreasing values from 0 to n
+// (empty streams, and runs of them, are legal).  Position i answers
+// rt_one(text, ..., i, start(i)) with start(i) the largest offs[j] <= i: the
+// walk of the other kernels with a stream start per position, which is what
+// read_char gives after a reset() at every stream's first byte.
+//
+// The launch is cut into 1,024-position tiles; lane k of the workgroup owns
+// position base + k of each of its tiles (a wave's store is 256 contiguous
+// bytes of u32 ids).  A workgroup takes a contiguous run of tiles, not every
+// G-th one: the offsets at or below the next tile's base then begin where
+// this tile's ended, so after one binary search per workgroup a tile costs
+// two scalar loads of offs when no stream begins inside it (a search per
+// tile is ~16 dependent loads, more than the tile's own work).  Per tile,
+// wave-uniform (readfirstlane, scalar):
+//   a = offsets <= base, b = offsets < the tile's end (batch_seek, galloping
+//   from the previous tile's b), start0 = offs[a - 1].
+// b == a: no stream begins inside the tile, every lane starts at start0.
+// Otherwise the lanes set one bit per offs[j], j in [a, b), in a 1,024-bit
+// LDS mask (32 words, atomicOr) and each lane's start is the highest set bit
+// at or below its own position -- its own word masked, then the words below
+// -- or start0 when there is none.  A tile of 1,024 one-byte streams sets
+// every bit and every lane finds its own.
+// Memory safety does not depend on the offsets: every index into offs is in
+// [0, nseg], a mask bit is set only for 0 < offs[j] - base < 1,024, and every
+// start is clamped into [0, i], so whatever offs holds the walk reads
+// text[0, i] only and the store goes to out[i], i < n.
+// SMALL (launches of at most RtDev::small_max positions, rt_small_kernel's
+// bound and reason): one tile per workgroup and the depth-2 answers from
+// global t12; else one workgroup per CU with the 64 Ki t12 entries staged in
+// LDS (128 KiB + the 128-B mask).
+// Measured (scripts/bench_batch.py, profiles/batch/; snort, 64 MiB ASCII, u32
+// ids / count only): 100 KiB streams 0.487 / 0.409 ms, 1,500-byte streams
+// 0.798 / 0.731 ms, one unsegmented rt_scan_kernel launch 0.108 / 0.087 ms.
+// One walk per lane with nothing else in flight: latency-bound on the depth-3
+// probes.  The variant with four consecutive positions per
+// lane from one text dword and a 16-B store per lane is not built, so there
+// is no second number to set beside these.
+constexpr int RT_BATCH_TILE = RT_THREADS;
+
+// First j in [lo, cnt) with offs[j] >= key, cnt when none (every j < lo is
+// known to fail): doubling steps from lo, then bisection.  Bounded by the
+// index range whatever offs holds.
+__device__ __forceinline__ int64_t batch_seek(const int64_t* __restrict__ offs, int64_t lo, int64_t cnt, int64_t key) {
+    int64_t hi = lo, step = 1;
+    while (hi < cnt && (int64_t)rfl64((uint64_t)offs[hi]) < key) {
+        lo = hi + 1;
+        hi += step;
+        step <<= 1;
+    }
+    if (hi > cnt) hi = cnt;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)rfl64((uint64_t)offs[mid]) < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <int OUTW, bool SMALL>
+__global__ __launch_bounds__(RT_THREADS) void rt_batch_kernel(const uint8_t* __restrict__ text,
+                                                              const int64_t* __restrict__ offs, int64_t nseg,
+                                                              int64_t n, void* __restrict__ out,
+                                                              unsigned long long* __restrict__ count, RtDev t) {
+    constexpr int kT12Words = SMALL ? 0 : RT_T2_U16 / 2;
+    __shared__ __attribute__((aligned(16))) uint32_t s_lds[kT12Words + RT_BATCH_TILE / 32];
+    uint32_t* const s_mask = s_lds + kT12Words;
+    const uint16_t* s_t = t.t12;
+    const int tid = threadIdx.x;
+    if (!SMALL) {
+        const uint4* src = reinterpret_cast<const uint4*>(t.t12);
+        uint4* dst = reinterpret_cast<uint4*>(s_lds);
+        for (int k = tid; k < RT_T2_U16 * 2 / 16; k += RT_THREADS) dst[k] = src[k];
+        __syncthreads();
+        s_t = reinterpret_cast<const uint16_t*>(s_lds);
+    }
+    // this workgroup's tiles [T0, T1): a contiguous share (wave-uniform)
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t T0 = ntiles * (int64_t)blockIdx.x / (int64_t)gridDim.x;
+    const int64_t T1 = ntiles * ((int64_t)blockIdx.x + 1) / (int64_t)gridDim.x;
+    const int64_t noffs = nseg + 1;
+    int64_t a = batch_seek(offs, 0, noffs, T0 * RT_BATCH_TILE + 1);
+    uint32_t cnt = 0;  // per lane
+    for (int64_t T = T0; T < T1; ++T) {
+        const int64_t base = T * RT_BATCH_TILE;
+        const int64_t end = base + RT_BATCH_TILE < n ? base + RT_BATCH_TILE : n;
+        a = batch_seek(offs, a, noffs, base + 1);       // offsets <= base (those equal to the last tile's end)
+        const int64_t b = batch_seek(offs, a, noffs, end);  // offsets < end: offs[a, b) begin inside the tile
+        int64_t start = a > 0 ? (int64_t)rfl64((uint64_t)offs[a - 1]) : 0;
+        if (b > a) {  // workgroup-uniform: every wave computed the same a and b
+            __syncthreads();  // the previous tile's readers are done
+            if (tid < RT_BATCH_TILE / 32) s_mask[tid] = 0u;
+            __syncthreads();
+            for (int64_t j = a + tid; j < b; j += RT_THREADS) {
+                const int64_t rel = offs[j] - base;
+                if (rel > 0 && rel < RT_BATCH_TILE) atomicOr(&s_mask[rel >> 5], 1u << (rel & 31));
+            }
+            __syncthreads();
+            int w = tid >> 5;
+            uint32_t m = s_mask[w] & (0xFFFFFFFFu >> (31 - (tid & 31)));
+            while (!m && w > 0) m = s_mask[--w];
+            if (m) start = base + w * 32 + 31 - __clz(m);
+        }
+        const int64_t i = base + tid;
+        uint32_t v = 0;
+        if (i < n) {
+            start = start < 0 ? 0 : start > i ? i : start;
+            v = rt_one(text, s_t, t, i, start);
+            if (OUTW) put_id<OUTW>(out, i, v);
+        }
+        cnt += v != 0u;
+        a = b;
+    }
+    if (count) {
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+        if ((tid & 63) == 0 && cnt) atomicAdd(count, (unsigned long long)cnt);
+    }
+}
+
 constexpr int DFA_THREADS = 256;
 
 template <int OUTW>
@@ -2745,6 +2865,32 @@ static hipError_t launch_rt_impl(bool floor, const uint8_t* text, int64_t stream
 hipError_t pm_launch_rt(const uint8_t* text, int64_t stream_start, int64_t pos0, int64_t n, void* out, int outw,
                         unsigned long long* count, const RtDev& t, int num_cu, hipStream_t s) {
     return launch_rt_impl(false, text, stream_start, pos0, n, out, outw, count, t, num_cu, s);
+}
+
+// The batched scan (rt_batch_kernel): at most small_max positions, one
+// 1,024-position tile per workgroup over the global tables; above, one
+// workgroup per CU, each over a contiguous share of the tiles.  No scratch,
+// nothing allocated: legal under stream capture.
+hipError_t pm_launch_rt_batch(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n, void* out,
+                              int outw, unsigned long long* count, const RtDev& t, int num_cu, hipStream_t s) {
+    if (n <= 0 || nseg <= 0) return hipSuccess;
+    if (!text || !offsets || num_cu <= 0) return hipErrorInvalidValue;
+    if (!out) outw = 0;
+    if (outw != 0 && outw != 2 && outw != 4) return hipErrorInvalidValue;
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
+    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
+    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+#define PM_BATCH_LAUNCH(W_)                                                                                         \
+    do {                                                                                                            \
+        if (small) hipLaunchKernelGGL((rt_batch_kernel<W_, true>), g, b, 0, s, text, offsets, nseg, n, out, count, t); \
+        else hipLaunchKernelGGL((rt_batch_kernel<W_, false>), g, b, 0, s, text, offsets, nseg, n, out, count, t);   \
+    } while (0)
+    if (outw == 4) PM_BATCH_LAUNCH(4);
+    else if (outw == 2) PM_BATCH_LAUNCH(2);
+    else PM_BATCH_LAUNCH(0);
+#undef PM_BATCH_LAUNCH
+    return hipGetLastError();
 }
 
 hipError_t pm_launch_rt_serve(PmServeReq* req, uint64_t* fwd, uint32_t* done, int blocks, uint64_t seen,

@@ -240,6 +240,18 @@ struct Server {
     int64_t idle_us = -1;  // option "serve_idle_us" (-1: PM_HOST_SERVE_IDLE_US, default 2,000)
     bool failed = false;   // its buffers could not be made: the object's calls launch
 };
+// Device staging of the host batch calls (pm_hip_read_batch*): the text, the
+// offsets and the u32 ids of one call, grown to the largest call, and a
+// stream of its own.  Plain copies from and to the caller's pageable memory
+// (the read_block slots' pinned staging is sized and carried per stream;
+// sharing it would change read_block's path).  Scratch (pm_hip_scratch_bytes).
+struct BatchStage {
+    uint8_t* d_text = nullptr;
+    int64_t* d_offs = nullptr;
+    uint32_t* d_out = nullptr;
+    size_t cap_n = 0, cap_offs = 0;  // positions / offsets the buffers hold
+    hipStream_t s = nullptr;
+};
 struct PmHip {
     int kind_req = KIND_RT;
     int kind = 0;
@@ -291,6 +303,7 @@ struct PmHip {
     int dfa_form = 0;
     uint64_t untimed_calls = 0;  // read_block launches since reset without timing events
     int last_sparse_kernel = 0;  // PmSparseKernel of the last sparse-form launch (0: none yet)
+    BatchStage batch;
 };
 
 // Drop the pick's choice and measurements (a measurement still in flight
@@ -1348,6 +1361,10 @@ void pm_hip_free(void* obj) {
     }
     if (o->d_lines_pats) (void)hipFree(o->d_lines_pats);
     if (o->d_lines_offs) (void)hipFree(o->d_lines_offs);
+    if (o->batch.d_text) (void)hipFree(o->batch.d_text);
+    if (o->batch.d_out) (void)hipFree(o->batch.d_out);
+    if (o->batch.d_offs) (void)hipFree(o->batch.d_offs);
+    if (o->batch.s) (void)hipStreamDestroy(o->batch.s);
     free_pick(o->pick);
     for (PipeSlot& q : o->slot) {
         free_slot(q);
@@ -1435,6 +1452,139 @@ int pm_hip_scan_device16(void* obj, const uint8_t* d_text, int64_t stream_start,
     return scan_device(obj, d_text, stream_start, pos0, n, d_out, 2, d_count, hip_stream);
 }
 
+// ---- batched scan: many independent streams in one launch ------------------
+// 0 when the object can run it; -1 before compile(); -6 when it holds no
+// reverse-trie image (the ac kind, or an rt / auto object compile() turned
+// into AC because the image did not fit): the batched scan is the
+// reverse-trie walk with a stream start per position, and a segmented DFA
+// walk is not implemented.
+static int batch_check(PmHip* o) {
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    if (o->kind != KIND_RT && o->kind != KIND_AUTO) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "the batched scan needs the reverse-trie image, which this object does not hold (the ac kind, "
+                      "or a dictionary past the reverse-trie encoding); a segmented DFA walk is not implemented");
+        return -6;
+    }
+    return 0;
+}
+
+static int scan_batch_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg, int64_t n,
+                             void* d_out, int outw, unsigned long long* d_count, void* hip_stream) {
+    PmHip* o = as(obj);
+    if (const int rc = batch_check(o)) return rc;
+    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_offsets & 7) ||
+        (nseg > 0 && n > 0 && (!d_text || !d_offsets))) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (nseg >= 0, n >= 0, text and ids 16-B aligned, offsets 8-B aligned)");
+        return -2;
+    }
+    if (outw == 2 && d_out && o->gids.index_of_gid.size() > 65536) {
+        std::snprintf(g_err, sizeof(g_err), "u16 ids need fewer than 65536 patterns (have %zu)",
+                      o->gids.index_of_gid.size() - 1);
+        return -4;
+    }
+    if (nseg == 0 || n == 0) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess)
+        e = pm_launch_rt_batch(d_text, d_offsets, nseg, n, d_out, outw, d_count, o->rt, o->num_cu,
+                               (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "batch launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_RT;
+    o->last_form = 0;
+    return 0;
+}
+
+int pm_hip_scan_batch_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg, int64_t n,
+                             uint32_t* d_out, unsigned long long* d_count, void* hip_stream) {
+    return scan_batch_device(obj, d_text, d_offsets, nseg, n, d_out, 4, d_count, hip_stream);
+}
+
+int pm_hip_scan_batch_device16(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg, int64_t n,
+                               uint16_t* d_out, unsigned long long* d_count, void* hip_stream) {
+    return scan_batch_device(obj, d_text, d_offsets, nseg, n, d_out, 2, d_count, hip_stream);
+}
+
+// The host forms: text and offsets to the object's staging, one batch launch,
+// the ids back, one synchronize.  Nothing read_block / read_char carry (the
+// history, the host step's state, the picks) is read or written.
+static int read_batch(PmHip* o, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* out_gid,
+                      pm_pattern_id_t* out_ids) {
+    if (const int rc = batch_check(o)) return rc;
+    bool ok = (nseg == 0 || (buf && offsets)) && (out_gid || out_ids || nseg == 0) && nseg < ((size_t)1 << 60);
+    if (ok && nseg) {
+        ok = offsets[0] == 0;
+        for (size_t j = 0; ok && j < nseg; ++j) ok = offsets[j] <= offsets[j + 1];
+    }
+    if (!ok) {
+        std::snprintf(g_err, sizeof(g_err), "bad arguments (offsets[0] == 0, offsets non-decreasing)");
+        return -2;
+    }
+    const size_t n = nseg ? (size_t)offsets[nseg] : 0;
+    if (n == 0) return 0;
+    PM_CHECK(hipSetDevice(o->device));
+    BatchStage& q = o->batch;
+    if (!q.s) PM_CHECK(hipStreamCreateWithFlags(&q.s, hipStreamNonBlocking));
+    if (n > q.cap_n) {
+        if (q.d_text) PM_CHECK(hipFree(q.d_text));
+        if (q.d_out) PM_CHECK(hipFree(q.d_out));
+        q.d_text = nullptr;
+        q.d_out = nullptr;
+        q.cap_n = 0;
+        const size_t cap = std::max(n, (size_t)1 << 16);
+        PM_CHECK(hipMalloc(&q.d_text, cap + 16));
+        PM_CHECK(hipMalloc(&q.d_out, cap * sizeof(uint32_t)));
+        q.cap_n = cap;
+    }
+    if (nseg + 1 > q.cap_offs) {
+        if (q.d_offs) PM_CHECK(hipFree(q.d_offs));
+        q.d_offs = nullptr;
+        q.cap_offs = 0;
+        const size_t cap = std::max(nseg + 1, (size_t)1 << 10);
+        PM_CHECK(hipMalloc(&q.d_offs, cap * sizeof(int64_t)));
+        q.cap_offs = cap;
+    }
+    serve_stop(o);  // a device launch wants the whole device
+    PM_CHECK(hipMemcpyAsync(q.d_text, buf, n, hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
+    const hipError_t e = pm_launch_rt_batch(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, q.d_out, 4, nullptr, o->rt,
+                                            o->num_cu, q.s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(q.s);
+        std::snprintf(g_err, sizeof(g_err), "batch launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_RT;
+    o->last_form = 0;
+    std::vector<uint32_t> tmp;
+    uint32_t* gid = out_gid;
+    if (!gid) {
+        tmp.resize(n);
+        gid = tmp.data();
+    }
+    PM_CHECK(hipMemcpyAsync(gid, q.d_out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, q.s));
+    PM_CHECK(hipStreamSynchronize(q.s));
+    if (!out_gid) {
+        const pm_pattern_id_t* map = o->id_of_gid.data();
+        par_range(n, (size_t)1 << 18, [&](size_t lo, size_t hi) {
+            for (size_t j = lo; j < hi; ++j) out_ids[j] = map[gid[j]];
+        });
+    }
+    return 0;
+}
+
+int pm_hip_read_batch_gid(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* out_gid) {
+    return read_batch(as(obj), buf, offsets, nseg, out_gid, nullptr);
+}
+
+int pm_hip_read_batch(void* obj, const char* buf, const int64_t* offsets, size_t nseg, pm_pattern_id_t* out) {
+    return read_batch(as(obj), reinterpret_cast<const uint8_t*>(buf), offsets, nseg, nullptr, out);
+}
+
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,
                         unsigned long long* d_counts, void* hip_stream) {
     PmHip* o = as(obj);
@@ -1487,6 +1637,8 @@ size_t pm_hip_scratch_bytes(void* obj) {
     for (const StreamSpill& x : o->sspill) b += (size_t)x.cap * 8;
     for (const PipeSlot& q : o->slot)
         b += (size_t)q.spill_cap * 8 + (q.d_stage ? q.cap * sizeof(uint32_t) + q.cap + o->max_len + 64 : 0);
+    if (o->batch.d_text) b += o->batch.cap_n + 16 + o->batch.cap_n * sizeof(uint32_t);
+    if (o->batch.d_offs) b += o->batch.cap_offs * sizeof(int64_t);
     return b;
 }
 

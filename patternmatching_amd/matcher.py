@@ -111,6 +111,16 @@ def gen_stream(n, seed, mode=0, offset=0):
     return buf
 
 
+def batch_offsets(buffers) -> np.ndarray:
+    """The offsets array of a list of bytes-like streams laid back to back
+    (HipMatcher.read_batch_*, scan_batch_device): len(buffers) + 1 int64
+    values, 0 first, the total length last.  Pure numpy, no device."""
+    lens = [b.size if isinstance(b, np.ndarray) else len(b) for b in buffers]
+    offs = np.zeros(len(lens) + 1, dtype=np.int64)
+    np.cumsum(np.asarray(lens, dtype=np.int64), out=offs[1:])
+    return offs
+
+
 class HipMatcher:
     """One GPU matcher instance ("rt" = reverse-trie kernel, "ac" = AC DFA,
     "auto" = both, picked per launch)."""
@@ -221,6 +231,68 @@ class HipMatcher:
         rc = fn(self.obj, d_text_ptr, stream_start, pos0, n, d_out_ptr, d_count_ptr, stream_ptr)
         if rc != 0:
             raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    # --- batched scan: many independent streams in one launch ------------
+    def scan_batch_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_out_ptr, d_count_ptr, stream_ptr, out_width=4):
+        """pm_hip_scan_batch_device / _device16: nseg streams back to back in
+        d_text[0, n), stream j = [offsets[j], offsets[j+1]) (nseg + 1 device
+        int64 values); dense ids of out_width bytes to d_out_ptr, or count
+        only.  Every stream is scanned from its own first byte."""
+        fn = {4: self.lib.pm_hip_scan_batch_device, 2: self.lib.pm_hip_scan_batch_device16}[out_width]
+        rc = fn(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_out_ptr, d_count_ptr, stream_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def read_batch_gids(self, data, offsets, out=None) -> np.ndarray:
+        """pm_hip_read_batch_gid: gids (u32) of the streams data[offsets[j]:
+        offsets[j+1]], each from its own start, in buffer order.  Leaves the
+        stream read_block / read_char carry untouched.  out: a contiguous u32
+        array of len(data) to fill instead of a new one (a caller in a loop
+        then pays no page faults of a fresh array per call)."""
+        arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
+                                   else data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or offs.size < 1 or int(offs[-1]) != len(arr):
+            raise ValueError("offsets: nseg + 1 values, the last one len(data)")
+        if out is None:
+            out = np.empty(len(arr), dtype=np.uint32)
+        elif out.dtype != np.uint32 or out.shape != (len(arr),) or not out.flags.c_contiguous:
+            raise ValueError("out: a contiguous uint32 array of len(data)")
+        rc = self.lib.pm_hip_read_batch_gid(self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                            offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), offs.size - 1,
+                                            out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        return out
+
+    def read_batch_codes(self, data, offsets) -> np.ndarray:
+        """(file << 24 | line) per position, like read_block_codes."""
+        return self._codes[self.read_batch_gids(data, offsets)]
+
+    def read_batch_id_array(self, data, offsets) -> np.ndarray:
+        """pm_hip_read_batch: the add_pattern id per position (uintp)."""
+        arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
+                                   else data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or offs.size < 1 or int(offs[-1]) != len(arr):
+            raise ValueError("offsets: nseg + 1 values, the last one len(data)")
+        out = np.empty(max(len(arr), 1), dtype=np.uintp)
+        rc = self.lib.pm_hip_read_batch(self.obj, arr.ctypes.data_as(ctypes.c_char_p),
+                                        offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), offs.size - 1,
+                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)))
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        return out[:len(arr)]
+
+    def read_many_codes(self, buffers):
+        """One batch call over a list of bytes-like streams; the codes of
+        each, in order."""
+        offs = batch_offsets(buffers)
+        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
+        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        codes = self.read_batch_codes(data, offs)
+        return [codes[offs[j]:offs[j + 1]] for j in range(len(buffers))]
 
     def gen_lines_device(self, d_dst_ptr, n, seed, stream_ptr):
         """pm_hip_gen_lines_device: the lines stream (random dictionary
