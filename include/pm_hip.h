@@ -118,8 +118,9 @@ int pm_hip_scan_device16(void* obj, const uint8_t* d_text, int64_t stream_start,
  *   -6  the object holds no reverse-trie image: the ac kind, and an rt / auto
  *       object whose dictionary compile() gave to the DFA because the
  *       reverse-trie encoding did not hold it.  The batched scan is the
- *       reverse-trie walk with a stream start per position; a segmented DFA
- *       walk is out of scope.  Nothing is launched, d_out is untouched and
+ *       reverse-trie walk with a stream start per position; the segmented DFA
+ *       walk is the flow scan below (pm_hip_scan_flows_device), which those
+ *       objects run.  Nothing is launched, d_out is untouched and
  *       pm_hip_last_error says why.
  * Launches of at most "rt_small_max" positions run one thread per position
  * over the global tables, larger ones one workgroup per CU (DESIGN.md §4,
@@ -141,6 +142,71 @@ int pm_hip_scan_batch_device16(void* obj, const uint8_t* d_text, const int64_t* 
  * middle of a stream is invisible to that stream.  Codes as above (-6 too). */
 int pm_hip_read_batch_gid(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* out_gid);
 int pm_hip_read_batch(void* obj, const char* buf, const int64_t* offsets, size_t nseg, pm_pattern_id_t* out);
+
+/*
+ * Flow scan: the batched layout with a carried state per stream, for flows
+ * whose bytes arrive a packet at a time among thousands of other flows.
+ * Text, offsets and output are exactly pm_hip_scan_batch_device's; each
+ * stream also brings a u32 state in and leaves one out.  A flow state is
+ * opaque: 0 means "at the start of a stream", any other value is one this
+ * object returned earlier for that flow.  The answer at position i of stream
+ * j is what read_char returns after reset(), every byte the flow had in
+ * earlier calls, and this call's bytes up to and including i (mpac.c:304-319:
+ * the automaton state kept across chunks, reset only at a new stream file,
+ * measure.c:241-311) -- so a pattern that straddles a packet boundary is
+ * found, which a batch call per packet misses.
+ *   d_state_in   DEVICE pointer, 4-byte aligned, nseg values, or NULL: every
+ *                stream fresh.  The device form does not check the values: a
+ *                state >= pm_hip_flow_states(obj) is used as 0.
+ *   d_state_out  DEVICE pointer, 4-byte aligned, nseg values, or NULL:
+ *                d_state_out[j] = the state after stream j's last byte; for
+ *                an empty stream the state it came in with.  Must not overlap
+ *                d_state_in (one lane reads state_in[j] while another writes
+ *                state_out[j]): callers ping-pong two arrays.
+ * A flow appears at most once per call (its state would be read once and
+ * written twice): a caller holding two packets of one flow concatenates them
+ * into one stream.  The walk runs over the DFA's dense rows (dfa_flow_kernel,
+ * DESIGN.md §4); on the DFA a flow's whole history is this one u32.
+ * Asynchronous, on hip_stream; needs no scratch and allocates nothing, so it
+ * may be captured into a graph.  It asks the resident read_block server to
+ * leave the device first, reads and changes nothing read_block / read_char
+ * carry, and leaves the auto kind's kernel pick alone.  Afterwards
+ * pm_hip_kernel_last is 2 and pm_hip_dfa_form_last is 1.
+ * nseg == 0: returns 0, launches nothing, the state arrays are untouched.
+ * n == 0 with nseg > 0: every stream is empty; the kernel's state-copy pass
+ * alone is launched (d_state_out[j] = d_state_in[j]), nothing when
+ * d_state_out is NULL.
+ * Returns 0, -1 before compile(), -2 bad arguments (negative nseg or n;
+ * alignment: text and ids 16 B, offsets 8 B, states 4 B; d_state_in ==
+ * d_state_out), -3 launch error, -4 u16 ids above 65,535 patterns, and
+ *   -6  the object holds no DFA image (the rt kind): nothing is launched or
+ *       written and pm_hip_last_error names the ac / auto kinds.
+ * The "flow_seg" option forces the lane segment length (tests, A/B timing).
+ */
+int pm_hip_scan_flows_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg, int64_t n,
+                             const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t* d_out,
+                             unsigned long long* d_count, void* hip_stream);
+/* The same with u16 gids; -4 above 65,535 patterns, as pm_hip_scan_device16. */
+int pm_hip_scan_flows_device16(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg, int64_t n,
+                               const uint32_t* d_state_in, uint32_t* d_state_out, uint16_t* d_out,
+                               unsigned long long* d_count, void* hip_stream);
+/* Host forms, as pm_hip_read_batch*: buf, offsets and state are HOST arrays;
+ * offsets is checked (offsets[0] == 0, non-decreasing) and so is every state
+ * (< pm_hip_flow_states), else -2 with nothing written.  state: nseg values,
+ * read as the streams' states in and overwritten with their states out (the
+ * call copies, so one array serves both), or NULL: every stream fresh and no
+ * state returned.  Text, offsets and ids use the batch calls' staging, the
+ * states two device buffers beside it (all in pm_hip_scratch_bytes); one flow
+ * launch, one synchronize.  n == 0: every stream keeps its state, so nothing
+ * is copied or launched.  pm_hip_read_flows maps the gids to the add_pattern
+ * ids as pm_hip_read_block does.  Codes as above (-6 too). */
+int pm_hip_read_flows_gid(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                          uint32_t* out_gid);
+int pm_hip_read_flows(void* obj, const char* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                      pm_pattern_id_t* out);
+/* Flow states of the object: valid states are 0 .. this - 1; 0 before
+ * compile() and without a DFA image (the rt kind). */
+uint32_t pm_hip_flow_states(void* obj);
 
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,
@@ -277,6 +343,8 @@ int pm_hip_set_device(int device);
  *                     (dfa_fl2_kernel; with fl_hold 1 or 2)
  *   "dfa_sync"        1 = DFA warm-ups start at the last synchronizing 3-gram
  *                     (default), 0 = max_len - 1 bytes back
+ *   "flow_seg"        the flow scan's lane segment length: 0 = the launcher's
+ *                     choice (default), else a multiple of 16 in [16, 4096]
  *   "rt_small_max"    reverse-trie launches of at most this many positions
  *                     run one thread per position (-1 = default 256 Ki,
  *                     0 = never)
@@ -340,6 +408,16 @@ size_t pm_flat_array(void* handle, const char* name, const void** data, size_t* 
  * the DFA step (its sparse form; dense rows when dense_rows != 0 or it has
  * none).  out_gid: n gids.  Returns 0, or -1 when the RT image does not fit. */
 int pm_flat_host_scan(void* handle, const uint8_t* text, size_t n, uint32_t* out_gid, int dense_rows);
+/* The flow scan's contract without a device, over the dense rows of a kind-2
+ * image: the semantics of pm_hip_scan_flows_device (host arrays; state_in
+ * may be NULL, state_out may be NULL or state_in; a state >=
+ * pm_flat_flow_states is used as 0, and an empty stream returns its state as
+ * used), and -- the image being the one compile() uploads -- the same state
+ * numbers.  offsets are not checked.  Returns 0, or -1 on a kind-1 image. */
+int pm_flat_host_scan_flows(void* handle, const uint8_t* text, const int64_t* offsets, size_t nseg,
+                            const uint32_t* state_in, uint32_t* state_out, uint32_t* out_gid);
+/* States of a kind-2 image (0 for kind 1). */
+uint32_t pm_flat_flow_states(void* handle);
 void pm_flat_free(void* handle);
 
 #ifdef __cplusplus

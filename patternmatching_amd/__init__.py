@@ -13,11 +13,14 @@ interface:
     gen_stream      the synthetic stream specification
     batch_offsets   the offsets array of a list of streams, for the batched
                     scan (HipMatcher.read_batch_* / scan_batch_device)
+    FlowTable       flow key -> carried state over the flow scan
+                    (HipMatcher.read_flows_* / scan_flows_device)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401
     Dictionary,
     HipMatcher,
+    FlowTable,
     gen_stream,
     batch_offsets,
     parse_line,
@@ -26,5 +29,5 @@ from .matcher import (  # noqa: F401
     KIND_AUTO,
 )
 
-__all__ = ["load", "Dictionary", "HipMatcher", "gen_stream", "batch_offsets", "parse_line", "KIND_RT", "KIND_AC",
-           "KIND_AUTO", "LIB_PATH", "CLI_PATH"]
+__all__ = ["load", "Dictionary", "HipMatcher", "FlowTable", "gen_stream", "batch_offsets", "parse_line", "KIND_RT",
+           "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]

@@ -94,6 +94,15 @@ SIGNATURES = {
     "pm_hip_read_batch_gid": (ctypes.c_int, [c_vp, c_u8p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, c_u32p]),
     "pm_hip_read_batch": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t,
                                          ctypes.POINTER(c_vp)]),
+    "pm_hip_scan_flows_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp, c_vp,
+                                                c_vp, c_vp]),
+    "pm_hip_scan_flows_device16": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp, c_vp,
+                                                  c_vp, c_vp]),
+    "pm_hip_read_flows_gid": (ctypes.c_int, [c_vp, c_u8p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, c_u32p,
+                                             c_u32p]),
+    "pm_hip_read_flows": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t,
+                                         c_u32p, ctypes.POINTER(c_vp)]),
+    "pm_hip_flow_states": (ctypes.c_uint32, [c_vp]),
     "pm_hip_score_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),
     "pm_hip_parent_gid": (ctypes.c_uint32, [c_vp, ctypes.c_uint32]),
     "pm_hip_set_image_cache": (None, [c_vp, ctypes.c_char_p]),
@@ -139,6 +148,9 @@ SIGNATURES = {
     "pm_hip_host_profile": (None, [ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     "pm_hip_scratch_bytes": (ctypes.c_size_t, [c_vp]),
     "pm_flat_host_scan": (ctypes.c_int, [c_vp, c_u8p, ctypes.c_size_t, c_u32p, ctypes.c_int]),
+    "pm_flat_host_scan_flows": (ctypes.c_int, [c_vp, c_u8p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, c_u32p,
+                                               c_u32p, c_u32p]),
+    "pm_flat_flow_states": (ctypes.c_uint32, [c_vp]),
 }
 
 _lib = None

@@ -116,6 +116,29 @@ uint32_t pm_dfa_host_step(const DfaImage& d, uint32_t& s, uint8_t c) {
     return d.out[s];
 }
 
+int pm_host_scan_flows(const DfaImage& d, const uint8_t* text, const int64_t* offsets, size_t nseg,
+                       const uint32_t* state_in, uint32_t* state_out, uint32_t* out_gid) {
+    if (d.next.empty() || d.out.empty()) return -1;
+    const bool coded = pm_dfa_coded(d.states);
+    for (size_t j = 0; j < nseg; ++j) {
+        uint32_t s = state_in ? state_in[j] : 0u;
+        if (s >= d.states) s = 0;
+        for (int64_t i = offsets[j]; i < offsets[j + 1]; ++i) {
+            const uint32_t x = d.next[(size_t)s * 256 + text[i]];
+            if (coded) {
+                s = x & PM_DFA_STATE_MASK;
+                const uint32_t code = x >> 20;
+                out_gid[i] = code != PM_DFA_ESC ? code : d.out[s];
+            } else {
+                s = x;
+                out_gid[i] = d.out[s];
+            }
+        }
+        if (state_out) state_out[j] = s;
+    }
+    return 0;
+}
+
 uint32_t pm_host_step(PmHostStep& h, PmHistRing& r, uint32_t max_len, uint8_t c) {
     if (h.kind == 1) {
         r.push(c);

@@ -85,6 +85,18 @@ uint32_t pm_rt_host_answer(const RtImage& im, const uint8_t* p, size_t avail);
 // the longest pattern ending at c.  State 0 is the root in both forms.
 uint32_t pm_dfa_host_step(const DfaImage& d, uint32_t& s, uint8_t c);
 
+// The flow scan on the host, over the dense rows (d.next / d.out, whatever
+// other forms d holds): nseg streams back to back in text, stream j = bytes
+// [offsets[j], offsets[j+1]) (offsets[0] == 0, non-decreasing; unchecked).
+// Stream j starts in state_in[j] (null: the root, 0; a value >= d.states is
+// used as 0) and state_out[j] (may be null, may be state_in) gets the state
+// after its last byte -- for an empty stream the state it came in with, as
+// used.  out_gid: offsets[nseg] gids.  The statement of the contract the
+// device kernel (pm_kernels.hip dfa_flow_kernel) is tested against.  0, or
+// -1 without dense rows.
+int pm_host_scan_flows(const DfaImage& d, const uint8_t* text, const int64_t* offsets, size_t nseg,
+                       const uint32_t* state_in, uint32_t* state_out, uint32_t* out_gid);
+
 // Host images kept for the step: the RT image, or the DFA (the sparse
 // form's block only, when it exists).
 struct PmHostStep {

@@ -111,6 +111,21 @@ hipError_t pm_launch_gather_probe(const uint32_t* table, uint32_t words, int ste
 // it), and for the sparse form DfaDev::sparse_kernel (0: the product choice).
 hipError_t pm_launch_dfa(const uint8_t* text, int64_t stream_start, int64_t pos0, int64_t n, void* out, int outw,
                          unsigned long long* count, const DfaDev& t, int num_cu, hipStream_t s);
+// Flow scan (dfa_flow_kernel): the batched layout of pm_launch_rt_batch over
+// the dense rows (t.next / t.out, `states` of them), with a carried state per
+// stream: stream j starts in state_in[j] (null: every stream at the root, 0)
+// and state_out[j] (may be null; must not overlap state_in) receives the state
+// after its last byte, state_in[j] for an empty stream.  An incoming state is
+// used as s < states ? s : 0.  force_seg: 0, or the lane segment length (a
+// multiple of 16 in [16, 4096]).  n == 0 with nseg > 0 launches the empty
+// streams' state copy alone.  Needs no scratch and allocates nothing.
+// Whatever offsets and state_in hold, reads stay in text[0, round_up(n, 16)),
+// offsets[0, nseg], state_in[0, nseg) and the tables, writes in out[0, n) and
+// state_out[0, nseg).
+hipError_t pm_launch_dfa_flows(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                               const uint32_t* state_in, uint32_t* state_out, void* out, int outw,
+                               unsigned long long* count, const DfaDev& t, uint32_t states, int64_t force_seg,
+                               int num_cu, hipStream_t s);
 // The sparse kernel (PmSparseKernel) a launch of this width runs, 0 when
 // it runs dense rows: the forced DfaDev::sparse_kernel where the object
 // and width allow it, else the product choice.

@@ -1651,6 +1651,169 @@ __global__ __launch_bounds__(DFA_THREADS) void dfa_coded_kernel(const uint8_t* _
     }
 }
 
+// The flow scan: the dense-row walk with a stream start per lane and a
+// carried state per stream.  text[0, n) holds nseg streams back to back
+// (offs as rt_batch_kernel's); stream j begins in state_in[j] (the root when
+// state_in is null) and leaves the state after its last byte in state_out[j].
+// The buffer is cut into lane segments of seg_len positions (a multiple of
+// 16).  The lane of [lo, hi) finds the stream j holding lo (flow_seek: the
+// first offset > lo, minus one, which skips runs of empty streams) and warms
+// up like dfa_coded_kernel, but never from before that stream's first byte:
+// wlo = max(lo - warm, offs[j]); a warm-up that reaches the stream's start
+// begins in state_in[j], any other at the root (exact from lo on: warm =
+// max_len - 1).  A synchronizing 3-gram inside [wlo, lo) shortens either
+// (dfa_sync_lo): the state after it does not depend on what came before, the
+// carried state included.  While it walks its output positions the lane keeps
+// `end`, the next stream end; after the step that consumes position end - 1
+// it stores state_out[j], seeks the next non-empty stream and reloads s from
+// its state_in.  Only the lane whose segment holds a stream's last byte
+// reaches that store, so each non-empty stream's state is written once, and
+// it is the state after every byte of the stream: the lane either started at
+// the stream's first byte in state_in[j], or at the root at least max_len - 1
+// bytes (or one synchronizing 3-gram) before lo, after which the DFA state is
+// the true one.  Empty streams copy their state in a grid-stride pass.
+// Aligned 16-position blocks inside the segment with no stream end before
+// their last position take one 16-B text load and 16-B id stores; every other
+// position goes byte-wise (a buffer of one-byte streams is legal and slow).
+//
+// Memory safety does not depend on offs or state_in: flow_seek's indices
+// are in [0, nseg], j is clamped into [0, nseg) before any offs[j], offs[j+1],
+// state_in[j] or state_out[j]; a walk starts at wlo clamped into [0, lo]; an
+// incoming state is used as s < states ? s : 0, and every table word's target
+// is a state, so row indices stay below states * 256; the 16-B text load at i
+// needs i + 16 <= hi <= n, the byte loads i < n; ids go to out[i], i < hi <=
+// n.  Offsets that are not sorted give unspecified ids and states, nothing
+// else (a stream end that never equals i is simply never taken).
+// One chain per lane, 1,024 lanes per CU (pm_launch_dfa_flows): the segments
+// of dfa_coded_kernel's 512 lanes x 2 chains.  88 VGPRs, no scratch, 5 waves
+// per SIMD.
+// Measured (scripts/bench_flows.py, profiles/flows/; 64 MiB in HBM, u32 ids,
+// a state in and out per stream, median of 20; 1,500-byte / 100 KiB streams
+// beside one unsegmented dfa_coded_kernel<4, 2, 32> launch over the same
+// bytes): snort ASCII 0.412 / 0.361 ms beside 0.345, snort lines 1.270 /
+// 1.230 beside 1.206, merged ASCII 0.435 / 0.381 beside 0.364, merged lines
+// 1.278 / 1.236 beside 1.201; count only, snort: 0.305 / 0.261 and 1.159 /
+// 1.118.  So one chain at twice the lanes is within 2-6% of the two-chain
+// dense kernel wherever the seek is amortised, and 19-20% behind on ASCII
+// with 44,740 streams (the per-lane seek, and one block in 94 byte-wise).
+// The two-chain variant (both chains' boundary blocks resolved in lock step)
+// is not built: those gaps bound what it could gain, and there is no second
+// number to set beside these.
+// batch_seek per lane: the same search, for lanes of one wave that look for
+// different keys (batch_seek's loads go through readfirstlane: wave-uniform
+// callers only).  First j in [lo, cnt) with offs[j] >= key, cnt when none.
+__device__ __forceinline__ int64_t flow_seek(const int64_t* __restrict__ offs, int64_t lo, int64_t cnt, int64_t key) {
+    int64_t hi = lo, step = 1;
+    while (hi < cnt && offs[hi] < key) {
+        lo = hi + 1;
+        hi += step;
+        step <<= 1;
+    }
+    if (hi > cnt) hi = cnt;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (offs[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+template <int OUTW, bool CODED>
+__global__ __launch_bounds__(DFA_THREADS) void dfa_flow_kernel(
+    const uint8_t* __restrict__ text, const int64_t* __restrict__ offs, int64_t nseg, int64_t n,
+    const uint32_t* __restrict__ state_in, uint32_t* __restrict__ state_out, void* __restrict__ out,
+    unsigned long long* __restrict__ count, const uint32_t* __restrict__ nxt, const uint32_t* __restrict__ outt,
+    uint32_t states, int64_t warm, int64_t seg_len, const uint32_t* __restrict__ gram3) {
+    const int64_t nlane = (n + seg_len - 1) / seg_len;
+    const int64_t stride = (int64_t)gridDim.x * DFA_THREADS;
+    const int64_t gtid = (int64_t)blockIdx.x * DFA_THREADS + threadIdx.x;
+    const int64_t noffs = nseg + 1;
+    auto load_state = [&](int64_t j) -> uint32_t {  // j in [0, nseg)
+        const uint32_t s = state_in ? state_in[j] : 0u;
+        return s < states ? s : 0u;
+    };
+    uint32_t cnt = 0;
+    for (int64_t sg = gtid; sg < nlane; sg += stride) {
+        const int64_t lo = sg * seg_len;
+        const int64_t hi = lo + seg_len < n ? lo + seg_len : n;
+        // the stream holding lo: the first offset > lo, minus one
+        int64_t j = flow_seek(offs, 0, noffs, lo + 1) - 1;
+        j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+        int64_t start = offs[j];
+        start = start < 0 ? 0 : start > lo ? lo : start;
+        int64_t end = offs[j + 1];
+        int64_t wlo = lo - warm;
+        if (wlo < start) wlo = start;
+        int64_t w = wlo;
+        if (gram3) w = dfa_sync_lo(text, lo, wlo, gram3);  // in [wlo, lo]: never before start
+        uint32_t s = (w == wlo && wlo == start) ? load_state(j) : 0u;
+        for (int64_t i = w; i < lo; ++i) {
+            const uint32_t v = nxt[(size_t)s * 256 + text[i]];
+            s = CODED ? v & DFA_STATE_MASK : v;
+        }
+        int64_t i = lo;
+        while (i < hi) {
+            if ((i & 15) == 0 && i + 16 <= hi && i + 16 <= end) {
+                const uint4 tw = *reinterpret_cast<const uint4*>(text + i);
+                const uint32_t W[4] = {tw.x, tw.y, tw.z, tw.w};
+                uint32_t r[16], st[16];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const uint32_t v = nxt[(size_t)s * 256 + ((W[q >> 2] >> (8 * (q & 3))) & 0xFFu)];
+                    s = CODED ? v & DFA_STATE_MASK : v;
+                    r[q] = CODED ? v >> 20 : 0u;
+                    st[q] = s;
+                }
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {  // count only: an escape code is a nonzero id, no lookup
+                    if (CODED) r[q] = OUTW && r[q] == DFA_ESC ? outt[st[q]] : r[q];
+                    else r[q] = outt[st[q]];
+                }
+                if (OUTW == 4) {
+                    uint4* o = reinterpret_cast<uint4*>(reinterpret_cast<uint32_t*>(out) + i);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) o[q] = make_uint4(r[4 * q], r[4 * q + 1], r[4 * q + 2], r[4 * q + 3]);
+                }
+                if (OUTW == 2) {
+                    uint4* o = reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(out) + i);
+#pragma unroll
+                    for (int q = 0; q < 2; ++q)
+                        o[q] = make_uint4(r[8 * q] | r[8 * q + 1] << 16, r[8 * q + 2] | r[8 * q + 3] << 16,
+                                          r[8 * q + 4] | r[8 * q + 5] << 16, r[8 * q + 6] | r[8 * q + 7] << 16);
+                }
+#pragma unroll
+                for (int q = 0; q < 16; ++q) cnt += r[q] != 0u;
+                i += 16;
+            } else {
+                const uint32_t v = nxt[(size_t)s * 256 + text[i]];
+                s = CODED ? v & DFA_STATE_MASK : v;
+                uint32_t id = CODED ? v >> 20 : outt[s];
+                if (CODED && OUTW && id == DFA_ESC) id = outt[s];
+                if (OUTW) put_id<OUTW>(out, i, id);
+                cnt += id != 0u;
+                ++i;
+            }
+            if (i == end) {  // position end - 1 was stream j's last byte
+                if (state_out) state_out[j] = s;
+                if (i < hi) {
+                    // the next stream that is not empty: the first offset > i, minus one
+                    j = flow_seek(offs, j + 2 < noffs ? j + 2 : noffs, noffs, i + 1) - 1;
+                    j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+                    end = offs[j + 1];
+                    s = load_state(j);
+                }
+            }
+        }
+    }
+    if (state_out)  // empty streams keep their state (as used: an invalid one is the root)
+        for (int64_t j = gtid; j < nseg; j += stride)
+            if (offs[j + 1] <= offs[j]) state_out[j] = load_state(j);
+    if (count) {
+        for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+        if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(count, (unsigned long long)cnt);
+    }
+}
+
 // The sparse (default-transition) form, pm_flatten.h: rows only for the
 // states whose row differs from their fallback's in more than PM_SDFA_K
 // bytes, 16-B records for the rest (8-B units in pm_pack_sparse8's
@@ -3068,6 +3231,51 @@ hipError_t pm_launch_dfa(const uint8_t* text, int64_t stream_start, int64_t pos0
         hipLaunchKernelGGL(dfa_scan_kernel<2>, g, b, 0, s, text, stream_start, pos0, n, out, count, t, seg);
     else
         hipLaunchKernelGGL(dfa_scan_kernel<0>, g, b, 0, s, text, stream_start, pos0, n, out, count, t, seg);
+    return hipGetLastError();
+}
+
+// The flow scan (dfa_flow_kernel) over the dense rows: segments as the dense
+// branch above cuts them -- one per lane at 1,024 lanes per CU (its 512 lanes
+// x 2 chains), none shorter than short_seg, whole 16-position blocks (32 with
+// ids) -- or force_seg (the "flow_seg" option) when it is not 0.  With n == 0
+// only the empty streams' state copy runs.  No scratch, nothing allocated.
+hipError_t pm_launch_dfa_flows(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                               const uint32_t* state_in, uint32_t* state_out, void* out, int outw,
+                               unsigned long long* count, const DfaDev& t, uint32_t states, int64_t force_seg,
+                               int num_cu, hipStream_t s) {
+    if (nseg <= 0 || n < 0 || (n == 0 && !state_out)) return hipSuccess;
+    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
+    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
+    if (!out) outw = 0;
+    if (outw != 0 && outw != 2 && outw != 4) return hipErrorInvalidValue;
+    const int64_t lanes = (int64_t)num_cu * DFA_LANES_PER_CU * DFA_CHAINS;
+    int64_t seg = (n + lanes - 1) / lanes;
+    const int64_t short_seg = std::min<int64_t>(512, std::max<int64_t>(n < (1 << 20) ? PM_DFA_SMALL_SEG : 64, n >> 16));
+    if (seg < short_seg) seg = short_seg;
+    const int64_t align = outw != 0 ? DFA_DENSE_BLK : 16;
+    seg = (seg + align - 1) / align * align;
+    if (force_seg) seg = force_seg;
+    const int64_t nlane = (n + seg - 1) / seg;
+    // (n == 0: the copy pass alone, a lane per stream up to one workgroup per CU)
+    int64_t blocks = n > 0 ? (nlane + DFA_THREADS - 1) / DFA_THREADS
+                           : std::min<int64_t>((nseg + DFA_THREADS - 1) / DFA_THREADS, num_cu);
+    if (blocks < 1) blocks = 1;
+    if (blocks > (int64_t)1 << 30) return hipErrorInvalidValue;
+    const dim3 g((unsigned)blocks), b(DFA_THREADS);
+    const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
+#define PM_FLOW_LAUNCH(W_, C_)                                                                                      \
+    hipLaunchKernelGGL((dfa_flow_kernel<W_, C_>), g, b, 0, s, text, offsets, nseg, n, state_in, state_out, out, count, \
+                       t.next, t.out, states, t.warm, seg, g3)
+    if (t.coded) {
+        if (outw == 4) PM_FLOW_LAUNCH(4, true);
+        else if (outw == 2) PM_FLOW_LAUNCH(2, true);
+        else PM_FLOW_LAUNCH(0, true);
+    } else {
+        if (outw == 4) PM_FLOW_LAUNCH(4, false);
+        else if (outw == 2) PM_FLOW_LAUNCH(2, false);
+        else PM_FLOW_LAUNCH(0, false);
+    }
+#undef PM_FLOW_LAUNCH
     return hipGetLastError();
 }
 

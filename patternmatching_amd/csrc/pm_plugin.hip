@@ -250,6 +250,10 @@ struct BatchStage {
     int64_t* d_offs = nullptr;
     uint32_t* d_out = nullptr;
     size_t cap_n = 0, cap_offs = 0;  // positions / offsets the buffers hold
+    // the flow calls' states in and out (pm_hip_read_flows*), cap_st of each
+    uint32_t* d_st_in = nullptr;
+    uint32_t* d_st_out = nullptr;
+    size_t cap_st = 0;
     hipStream_t s = nullptr;
 };
 struct PmHip {
@@ -304,6 +308,8 @@ struct PmHip {
     uint64_t untimed_calls = 0;  // read_block launches since reset without timing events
     int last_sparse_kernel = 0;  // PmSparseKernel of the last sparse-form launch (0: none yet)
     BatchStage batch;
+    uint32_t dfa_states = 0;  // states of the DFA image on the device (0: none); pm_hip_flow_states
+    int64_t flow_seg = 0;     // option "flow_seg": the flow scan's lane segment (0: the launcher's choice)
 };
 
 // Drop the pick's choice and measurements (a measurement still in flight
@@ -1243,6 +1249,7 @@ void pm_hip_compile(void* obj) {
             o->dfa.gram3 = (const uint32_t*)dalloc_copy(o, g3.data(), g3.size() * 4);
         }
         o->dfa.coded = pm_dfa_coded(im.dfa.states) ? 1 : 0;
+        o->dfa_states = im.dfa.states;
         if (!im.dfa.sblock.empty()) {
             // (+64 zero bytes: the LDS kernel reads records in aligned
             // blocks of four, the last one past the table's end)
@@ -1364,6 +1371,8 @@ void pm_hip_free(void* obj) {
     if (o->batch.d_text) (void)hipFree(o->batch.d_text);
     if (o->batch.d_out) (void)hipFree(o->batch.d_out);
     if (o->batch.d_offs) (void)hipFree(o->batch.d_offs);
+    if (o->batch.d_st_in) (void)hipFree(o->batch.d_st_in);
+    if (o->batch.d_st_out) (void)hipFree(o->batch.d_st_out);
     if (o->batch.s) (void)hipStreamDestroy(o->batch.s);
     free_pick(o->pick);
     for (PipeSlot& q : o->slot) {
@@ -1456,8 +1465,8 @@ int pm_hip_scan_device16(void* obj, const uint8_t* d_text, int64_t stream_start,
 // 0 when the object can run it; -1 before compile(); -6 when it holds no
 // reverse-trie image (the ac kind, or an rt / auto object compile() turned
 // into AC because the image did not fit): the batched scan is the
-// reverse-trie walk with a stream start per position, and a segmented DFA
-// walk is not implemented.
+// reverse-trie walk with a stream start per position; the segmented DFA walk
+// is the flow scan below (pm_hip_scan_flows_device), an entry point of its own.
 static int batch_check(PmHip* o) {
     if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
     if (o->kind != KIND_RT && o->kind != KIND_AUTO) {
@@ -1509,25 +1518,9 @@ int pm_hip_scan_batch_device16(void* obj, const uint8_t* d_text, const int64_t* 
     return scan_batch_device(obj, d_text, d_offsets, nseg, n, d_out, 2, d_count, hip_stream);
 }
 
-// The host forms: text and offsets to the object's staging, one batch launch,
-// the ids back, one synchronize.  Nothing read_block / read_char carry (the
-// history, the host step's state, the picks) is read or written.
-static int read_batch(PmHip* o, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* out_gid,
-                      pm_pattern_id_t* out_ids) {
-    if (const int rc = batch_check(o)) return rc;
-    bool ok = (nseg == 0 || (buf && offsets)) && (out_gid || out_ids || nseg == 0) && nseg < ((size_t)1 << 60);
-    if (ok && nseg) {
-        ok = offsets[0] == 0;
-        for (size_t j = 0; ok && j < nseg; ++j) ok = offsets[j] <= offsets[j + 1];
-    }
-    if (!ok) {
-        std::snprintf(g_err, sizeof(g_err), "bad arguments (offsets[0] == 0, offsets non-decreasing)");
-        return -2;
-    }
-    const size_t n = nseg ? (size_t)offsets[nseg] : 0;
-    if (n == 0) return 0;
-    PM_CHECK(hipSetDevice(o->device));
-    BatchStage& q = o->batch;
+// The staging of a host batch / flow call of n positions and nseg streams:
+// its stream, and buffers grown to the largest call so far.
+static void batch_stage_grow(BatchStage& q, size_t n, size_t nseg) {
     if (!q.s) PM_CHECK(hipStreamCreateWithFlags(&q.s, hipStreamNonBlocking));
     if (n > q.cap_n) {
         if (q.d_text) PM_CHECK(hipFree(q.d_text));
@@ -1548,6 +1541,28 @@ static int read_batch(PmHip* o, const uint8_t* buf, const int64_t* offsets, size
         PM_CHECK(hipMalloc(&q.d_offs, cap * sizeof(int64_t)));
         q.cap_offs = cap;
     }
+}
+
+// The host forms: text and offsets to the object's staging, one batch launch,
+// the ids back, one synchronize.  Nothing read_block / read_char carry (the
+// history, the host step's state, the picks) is read or written.
+static int read_batch(PmHip* o, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* out_gid,
+                      pm_pattern_id_t* out_ids) {
+    if (const int rc = batch_check(o)) return rc;
+    bool ok = (nseg == 0 || (buf && offsets)) && (out_gid || out_ids || nseg == 0) && nseg < ((size_t)1 << 60);
+    if (ok && nseg) {
+        ok = offsets[0] == 0;
+        for (size_t j = 0; ok && j < nseg; ++j) ok = offsets[j] <= offsets[j + 1];
+    }
+    if (!ok) {
+        std::snprintf(g_err, sizeof(g_err), "bad arguments (offsets[0] == 0, offsets non-decreasing)");
+        return -2;
+    }
+    const size_t n = nseg ? (size_t)offsets[nseg] : 0;
+    if (n == 0) return 0;
+    PM_CHECK(hipSetDevice(o->device));
+    BatchStage& q = o->batch;
+    batch_stage_grow(q, n, nseg);
     serve_stop(o);  // a device launch wants the whole device
     PM_CHECK(hipMemcpyAsync(q.d_text, buf, n, hipMemcpyHostToDevice, q.s));
     PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
@@ -1583,6 +1598,150 @@ int pm_hip_read_batch_gid(void* obj, const uint8_t* buf, const int64_t* offsets,
 
 int pm_hip_read_batch(void* obj, const char* buf, const int64_t* offsets, size_t nseg, pm_pattern_id_t* out) {
     return read_batch(as(obj), reinterpret_cast<const uint8_t*>(buf), offsets, nseg, nullptr, out);
+}
+
+// ---- flow scan: the batched layout with a carried state per stream ---------
+// 0 when the object can run it; -1 before compile(); -6 when it holds no DFA
+// image (the rt kind): a flow's carried state is a DFA state.
+static int flows_check(PmHip* o) {
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    if (!o->dfa.next || !o->dfa_states) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "the flow scan needs the DFA image, which this object does not hold (the rt kind); make the "
+                      "object with the ac or auto kind");
+        return -6;
+    }
+    return 0;
+}
+
+static int scan_flows_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg, int64_t n,
+                             const uint32_t* d_state_in, uint32_t* d_state_out, void* d_out, int outw,
+                             unsigned long long* d_count, void* hip_stream) {
+    PmHip* o = as(obj);
+    if (const int rc = flows_check(o)) return rc;
+    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_offsets & 7) ||
+        ((uintptr_t)d_state_in & 3) || ((uintptr_t)d_state_out & 3) || (d_state_in && d_state_in == d_state_out) ||
+        (nseg > 0 && (!d_offsets || (n > 0 && !d_text)))) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (nseg >= 0, n >= 0, text and ids 16-B aligned, offsets 8-B aligned, states 4-B "
+                      "aligned, state_in != state_out)");
+        return -2;
+    }
+    if (outw == 2 && d_out && o->gids.index_of_gid.size() > 65536) {
+        std::snprintf(g_err, sizeof(g_err), "u16 ids need fewer than 65536 patterns (have %zu)",
+                      o->gids.index_of_gid.size() - 1);
+        return -4;
+    }
+    // n == 0: the empty streams still hand their state on (the copy pass of
+    // the same kernel, pm_launch_dfa_flows)
+    if (nseg == 0 || (n == 0 && !d_state_out)) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess)
+        e = pm_launch_dfa_flows(d_text, d_offsets, nseg, n, d_state_in, d_state_out, d_out, outw, d_count, o->dfa,
+                                o->dfa_states, o->flow_seg, o->num_cu, (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "flow launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_AC;
+    o->last_form = 1;
+    return 0;
+}
+
+int pm_hip_scan_flows_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg, int64_t n,
+                             const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t* d_out,
+                             unsigned long long* d_count, void* hip_stream) {
+    return scan_flows_device(obj, d_text, d_offsets, nseg, n, d_state_in, d_state_out, d_out, 4, d_count, hip_stream);
+}
+
+int pm_hip_scan_flows_device16(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg, int64_t n,
+                               const uint32_t* d_state_in, uint32_t* d_state_out, uint16_t* d_out,
+                               unsigned long long* d_count, void* hip_stream) {
+    return scan_flows_device(obj, d_text, d_offsets, nseg, n, d_state_in, d_state_out, d_out, 2, d_count, hip_stream);
+}
+
+uint32_t pm_hip_flow_states(void* obj) {
+    PmHip* o = as(obj);
+    return o->compiled && o->dfa.next ? o->dfa_states : 0u;
+}
+
+// The host forms: text, offsets and states to the batch staging, one flow
+// launch, ids and states back, one synchronize.  Nothing read_block /
+// read_char carry is read or written.  Everything is checked before anything
+// is written.  n == 0: every stream is empty and keeps its state, which the
+// caller's array already holds -- nothing is copied or launched.
+static int read_flows(PmHip* o, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                      uint32_t* out_gid, pm_pattern_id_t* out_ids) {
+    if (const int rc = flows_check(o)) return rc;
+    bool ok = (nseg == 0 || offsets) && nseg < ((size_t)1 << 60);
+    if (ok && nseg) {
+        ok = offsets[0] == 0;
+        for (size_t j = 0; ok && j < nseg; ++j) ok = offsets[j] <= offsets[j + 1];
+        if (ok && offsets[nseg] > 0) ok = buf && (out_gid || out_ids);
+        if (ok && state)
+            for (size_t j = 0; ok && j < nseg; ++j) ok = state[j] < o->dfa_states;
+    }
+    if (!ok) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (offsets[0] == 0, offsets non-decreasing, every state below pm_hip_flow_states)");
+        return -2;
+    }
+    const size_t n = nseg ? (size_t)offsets[nseg] : 0;
+    if (n == 0) return 0;
+    PM_CHECK(hipSetDevice(o->device));
+    BatchStage& q = o->batch;
+    batch_stage_grow(q, n, nseg);
+    if (state && nseg > q.cap_st) {
+        if (q.d_st_in) PM_CHECK(hipFree(q.d_st_in));
+        if (q.d_st_out) PM_CHECK(hipFree(q.d_st_out));
+        q.d_st_in = q.d_st_out = nullptr;
+        q.cap_st = 0;
+        const size_t cap = std::max(nseg, (size_t)1 << 10);
+        PM_CHECK(hipMalloc(&q.d_st_in, cap * sizeof(uint32_t)));
+        PM_CHECK(hipMalloc(&q.d_st_out, cap * sizeof(uint32_t)));
+        q.cap_st = cap;
+    }
+    serve_stop(o);  // a device launch wants the whole device
+    PM_CHECK(hipMemcpyAsync(q.d_text, buf, n, hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
+    if (state) PM_CHECK(hipMemcpyAsync(q.d_st_in, state, nseg * sizeof(uint32_t), hipMemcpyHostToDevice, q.s));
+    const hipError_t e = pm_launch_dfa_flows(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, state ? q.d_st_in : nullptr,
+                                             state ? q.d_st_out : nullptr, q.d_out, 4, nullptr, o->dfa, o->dfa_states,
+                                             o->flow_seg, o->num_cu, q.s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(q.s);
+        std::snprintf(g_err, sizeof(g_err), "flow launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_AC;
+    o->last_form = 1;
+    std::vector<uint32_t> tmp;
+    uint32_t* gid = out_gid;
+    if (!gid) {
+        tmp.resize(n);
+        gid = tmp.data();
+    }
+    PM_CHECK(hipMemcpyAsync(gid, q.d_out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, q.s));
+    if (state) PM_CHECK(hipMemcpyAsync(state, q.d_st_out, nseg * sizeof(uint32_t), hipMemcpyDeviceToHost, q.s));
+    PM_CHECK(hipStreamSynchronize(q.s));
+    if (!out_gid) {
+        const pm_pattern_id_t* map = o->id_of_gid.data();
+        par_range(n, (size_t)1 << 18, [&](size_t lo, size_t hi) {
+            for (size_t j = lo; j < hi; ++j) out_ids[j] = map[gid[j]];
+        });
+    }
+    return 0;
+}
+
+int pm_hip_read_flows_gid(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                          uint32_t* out_gid) {
+    return read_flows(as(obj), buf, offsets, nseg, state, out_gid, nullptr);
+}
+
+int pm_hip_read_flows(void* obj, const char* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                      pm_pattern_id_t* out) {
+    return read_flows(as(obj), reinterpret_cast<const uint8_t*>(buf), offsets, nseg, state, nullptr, out);
 }
 
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,
@@ -1639,6 +1798,7 @@ size_t pm_hip_scratch_bytes(void* obj) {
         b += (size_t)q.spill_cap * 8 + (q.d_stage ? q.cap * sizeof(uint32_t) + q.cap + o->max_len + 64 : 0);
     if (o->batch.d_text) b += o->batch.cap_n + 16 + o->batch.cap_n * sizeof(uint32_t);
     if (o->batch.d_offs) b += o->batch.cap_offs * sizeof(int64_t);
+    if (o->batch.d_st_in) b += 2 * o->batch.cap_st * sizeof(uint32_t);
     return b;
 }
 
@@ -1738,6 +1898,11 @@ int pm_hip_set_option(void* obj, const char* name, int64_t value) {
     if (k == "dfa_sync") {
         if (value < 0 || value > 1) return -1;
         o->dfa.sync = (int)value;
+        return 0;
+    }
+    if (k == "flow_seg") {  // the flow scan's lane segment (tests, A/B timing)
+        if (value != 0 && (value < 16 || value > 4096 || value % 16)) return -1;
+        o->flow_seg = value;
         return 0;
     }
     if (k == "rt_small_max") {
@@ -1986,6 +2151,21 @@ int pm_flat_host_scan(void* handle, const uint8_t* text, size_t n, uint32_t* out
     r.init(max_len);
     for (size_t k = 0; k < n; ++k) out_gid[k] = pm_host_step(st, r, max_len, text[k]);
     return 0;
+}
+
+// The flow scan's contract on the host (pm_hoststep.h pm_host_scan_flows)
+// over the dense rows of a kind-2 image: the device form's semantics and,
+// the image being the same, its state numbers.  -1 on a kind-1 image.
+int pm_flat_host_scan_flows(void* handle, const uint8_t* text, const int64_t* offsets, size_t nseg,
+                            const uint32_t* state_in, uint32_t* state_out, uint32_t* out_gid) {
+    PmFlatHandle* h = static_cast<PmFlatHandle*>(handle);
+    if (h->kind != 2 || h->dfa.next.empty()) return -1;
+    return pm_host_scan_flows(h->dfa, text, offsets, nseg, state_in, state_out, out_gid);
+}
+
+uint32_t pm_flat_flow_states(void* handle) {
+    PmFlatHandle* h = static_cast<PmFlatHandle*>(handle);
+    return h->kind == 2 && !h->dfa.next.empty() ? h->dfa.states : 0u;
 }
 
 void pm_flat_free(void* handle) { delete static_cast<PmFlatHandle*>(handle); }

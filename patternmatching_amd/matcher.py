@@ -121,6 +121,54 @@ def batch_offsets(buffers) -> np.ndarray:
     return offs
 
 
+class FlowTable:
+    """The carried states of many live flows over one matcher (ac / auto
+    kinds): a dict of flow key -> flow state, and one flow call
+    (HipMatcher.read_flows_codes) per scan().
+
+        flows = FlowTable(m)
+        codes = flows.scan([(key, packet_bytes), ...])   # one array per packet
+        flows.end(key)                                    # the flow is over
+
+    A key seen for the first time starts a fresh flow.  A key may appear once
+    per scan(): two packets of one flow are concatenated by the caller."""
+
+    def __init__(self, matcher):
+        self.matcher = matcher
+        self.states = {}
+
+    def scan(self, packets):
+        """packets: a list of (key, bytes-like).  Returns the codes of each
+        packet, in order, every flow continued from its earlier packets."""
+        keys = [k for k, _ in packets]
+        if len(set(keys)) != len(keys):
+            seen = set()
+            dup = next(k for k in keys if k in seen or seen.add(k))
+            raise ValueError(f"flow {dup!r} appears twice in one scan(): concatenate its packets")
+        if not packets:
+            return []
+        bufs = [b for _, b in packets]
+        offs = batch_offsets(bufs)
+        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in bufs]
+        data = np.concatenate(parts)
+        state = np.array([self.states.get(k, 0) for k in keys], dtype=np.uint32)
+        codes, state = self.matcher.read_flows_codes(data, offs, state)
+        for k, s in zip(keys, state.tolist()):
+            self.states[k] = s
+        return [codes[offs[j]:offs[j + 1]] for j in range(len(packets))]
+
+    def end(self, key):
+        """Forget a flow: its key, seen again, starts a fresh one."""
+        self.states.pop(key, None)
+
+    def __len__(self):
+        return len(self.states)
+
+    def __contains__(self, key):
+        return key in self.states
+
+
 class HipMatcher:
     """One GPU matcher instance ("rt" = reverse-trie kernel, "ac" = AC DFA,
     "auto" = both, picked per launch)."""
@@ -293,6 +341,77 @@ class HipMatcher:
         data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
         codes = self.read_batch_codes(data, offs)
         return [codes[offs[j]:offs[j + 1]] for j in range(len(buffers))]
+
+    # --- flow scan: the batched layout with a carried state per stream -----
+    def scan_flows_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr, d_out_ptr,
+                          d_count_ptr, stream_ptr, out_width=4):
+        """pm_hip_scan_flows_device / _device16: scan_batch_device's layout,
+        but stream j starts in the state d_state_in[j] (u32 on the device;
+        None = every stream fresh) and leaves the state after its last byte
+        in d_state_out[j] (None = not wanted).  The two arrays must differ.
+        ac / auto kinds."""
+        fn = {4: self.lib.pm_hip_scan_flows_device, 2: self.lib.pm_hip_scan_flows_device16}[out_width]
+        rc = fn(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr, d_out_ptr, d_count_ptr,
+                stream_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def read_flows_gids(self, data, offsets, state=None):
+        """pm_hip_read_flows_gid: (gids, state_out).  Stream j = data[offsets[j]:
+        offsets[j+1]] continues the flow whose state is state[j] (a u32 array
+        of nseg values this object returned earlier, 0 = a fresh flow; None =
+        all fresh); state_out is always a new array, to hand back with the
+        flows' next packets.  A flow appears at most once per call."""
+        arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
+                                   else data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or offs.size < 1 or int(offs[-1]) != len(arr):
+            raise ValueError("offsets: nseg + 1 values, the last one len(data)")
+        nseg = offs.size - 1
+        st = np.zeros(nseg, dtype=np.uint32) if state is None else np.array(state, dtype=np.uint32, order="C")
+        if st.shape != (nseg,):
+            raise ValueError("state: nseg values")
+        out = np.empty(len(arr), dtype=np.uint32)
+        rc = self.lib.pm_hip_read_flows_gid(self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                            offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg,
+                                            st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                            out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        return out, st
+
+    def read_flows_codes(self, data, offsets, state=None):
+        """(codes, state_out): (file << 24 | line) per position, like
+        read_block_codes, and the flows' states."""
+        gids, st = self.read_flows_gids(data, offsets, state)
+        return self._codes[gids], st
+
+    def read_flows_id_array(self, data, offsets, state=None):
+        """pm_hip_read_flows: (the add_pattern id per position (uintp),
+        state_out)."""
+        arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
+                                   else data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or offs.size < 1 or int(offs[-1]) != len(arr):
+            raise ValueError("offsets: nseg + 1 values, the last one len(data)")
+        nseg = offs.size - 1
+        st = np.zeros(nseg, dtype=np.uint32) if state is None else np.array(state, dtype=np.uint32, order="C")
+        if st.shape != (nseg,):
+            raise ValueError("state: nseg values")
+        out = np.empty(max(len(arr), 1), dtype=np.uintp)
+        rc = self.lib.pm_hip_read_flows(self.obj, arr.ctypes.data_as(ctypes.c_char_p),
+                                        offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg,
+                                        st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)))
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        return out[:len(arr)], st
+
+    @property
+    def flow_states(self):
+        """pm_hip_flow_states: valid flow states are 0 .. this - 1 (0 for an
+        object without a DFA image)."""
+        return self.lib.pm_hip_flow_states(self.obj)
 
     def gen_lines_device(self, d_dst_ptr, n, seed, stream_ptr):
         """pm_hip_gen_lines_device: the lines stream (random dictionary
