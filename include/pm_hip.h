@@ -208,6 +208,75 @@ int pm_hip_read_flows(void* obj, const char* buf, const int64_t* offsets, size_t
  * compile() and without a DFA image (the rt kind). */
 uint32_t pm_hip_flow_states(void* obj);
 
+/*
+ * Match list: the batched and the flow scan with a compacted output for
+ * callers that want the few positions where a real pattern ends, not an id
+ * per byte (an IDS over packets, flows or log lines; dictionaries with 1- and
+ * 2-byte patterns answer 92-99% of all positions).  An event is one uint64_t,
+ * position << 24 | gid: the position is an index into the call's buffer, as
+ * for the dense outputs, so plain u64 order is position order, and there is
+ * at most one event per position.  Position i emits an event iff its answer
+ * g != 0 and pm_hip_pattern_len(g) >= min_len.  The answer is the longest
+ * pattern ending at i, so this is "some pattern of at least min_len bytes
+ * ends here" and the filter loses nothing; with min_len >= 3 the patterns of
+ * <= 2 bytes, whose gids come first, are rejected by one compare.
+ * Text, offsets and states mean exactly what they mean in
+ * pm_hip_scan_batch_device / pm_hip_scan_flows_device, with the same memory
+ * safety whatever the offsets hold; with nseg == 1 the calls serve a plain
+ * stream, for every kind between them.
+ *   min_len     >= 1.
+ *   d_events    DEVICE pointer, 8-byte aligned, cap events; NULL with cap == 0
+ *               for a count only.
+ *   d_nevents   DEVICE u64, required: the list's cursor.  Each event takes the
+ *               next slot from it (atomicAdd, reserved by a wave for many
+ *               events at a time) and is stored only when the slot is below
+ *               cap.  After the call it holds its old value plus ALL events
+ *               found: the caller zeroes it for a fresh list, or leaves it
+ *               and the call appends to an earlier list.  A value above cap
+ *               means the list was cut short; which events were kept is then
+ *               unspecified, and nothing at or beyond d_events[cap] is written.
+ * Order in the list is unspecified.  Asynchronous, on hip_stream; allocates
+ * nothing (the u32 length per gid is uploaded by compile() and counted in
+ * pm_hip_table_bytes), so the calls may be captured into a graph.  Like their
+ * dense siblings they ask the resident read_block server to leave the device
+ * first, and pm_hip_kernel_last / pm_hip_dfa_form_last read afterwards as
+ * after those.  nseg == 0: returns 0, launches nothing.  n == 0 with
+ * nseg > 0: the flow form's state-copy pass alone, as pm_hip_scan_flows_device.
+ * Returns 0, and as the dense siblings -1 before compile(), -2 bad arguments
+ * (theirs, and min_len == 0, d_nevents NULL, d_events misaligned or NULL with
+ * cap > 0, n > 2^40), -3 launch error, -6 the kind without the needed image
+ * (batch: ac; flows: rt), and -4 when the dictionary has 2^24 or more patterns.
+ * Measured (64 MiB, profiles/events/): on random ASCII (an event per 1,000
+ * bytes at min_len 3) the calls take 0.77-0.94x the time of their dense u32
+ * siblings.  Where such matches are dense (the lines stream: an event per 6-7
+ * bytes, 8 B each) they take 0.98-1.08x and hand back as many bytes: a caller
+ * with match-dense input keeps the ids.
+ */
+int pm_hip_scan_batch_events_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, uint32_t min_len, uint64_t* d_events, uint64_t cap,
+                                    unsigned long long* d_nevents, void* hip_stream);
+int pm_hip_scan_flows_events_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t min_len,
+                                    uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                    void* hip_stream);
+/* Bytes of pattern gid; 0 when out of range (gid 0 too) and before compile(). */
+uint32_t pm_hip_pattern_len(void* obj, uint32_t gid);
+/* Host forms, as pm_hip_read_batch_gid / pm_hip_read_flows_gid: buf, offsets
+ * and state are HOST arrays, validated as there (-2, nothing written), with
+ * the same staging plus an events buffer (all in pm_hip_scratch_bytes).
+ * *nevents = the total found; events gets the first min(cap, total) of them
+ * in ascending position order (the host form sorts).  The device list has to
+ * be complete for that: the first launch gives it max(1024, n / 16) events
+ * (the "events_cap" option overrides it), and a launch that finds more is
+ * repeated once with room for all of them, from the same input states -- they
+ * come in and leave through two device arrays.  The states written back are
+ * those of the complete scan.  Only the events come back over the link, not
+ * 4 n bytes of ids. */
+int pm_hip_read_batch_events(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t min_len,
+                             uint64_t* events, size_t cap, size_t* nevents);
+int pm_hip_read_flows_events(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                             uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents);
+
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,
  * PatternsTree.c:485-494): per position, equal -> success; d_algo's pattern
@@ -345,6 +414,9 @@ int pm_hip_set_device(int device);
  *                     (default), 0 = max_len - 1 bytes back
  *   "flow_seg"        the flow scan's lane segment length: 0 = the launcher's
  *                     choice (default), else a multiple of 16 in [16, 4096]
+ *   "events_cap"      the device capacity, in events, of the host events
+ *                     forms' first launch (pm_hip_read_*_events): 0 = the
+ *                     default max(1024, n / 16); tests force the second launch
  *   "rt_small_max"    reverse-trie launches of at most this many positions
  *                     run one thread per position (-1 = default 256 Ki,
  *                     0 = never)
@@ -400,7 +472,8 @@ int pm_flat_cache_hit(void* handle);
 int pm_flat_fits(void* handle);
 /* States with full rows in the sparse DFA form (0 when it has none). */
 uint32_t pm_flat_dfa_sparse_rows(void* handle);
-/* name: "t12" "filt" "t3h" "rec" "next" "out" "sblock" "sout" "index_of_gid" "parent" "depth";
+/* name: "t12" "filt" "t3h" "rec" "next" "out" "sblock" "sout" "index_of_gid" "parent" "depth"
+ * "len" (u32 bytes per gid, [0] = 0: the vector compile() uploads for the events forms);
  * returns element count */
 size_t pm_flat_array(void* handle, const char* name, const void** data, size_t* elem_size);
 /* read_char's host step (the per-byte path, csrc/pm_hoststep.h) over a
@@ -418,6 +491,9 @@ int pm_flat_host_scan_flows(void* handle, const uint8_t* text, const int64_t* of
                             const uint32_t* state_in, uint32_t* state_out, uint32_t* out_gid);
 /* States of a kind-2 image (0 for kind 1). */
 uint32_t pm_flat_flow_states(void* handle);
+/* n_short: gids 1 .. n_short are exactly the patterns of <= 2 bytes (the
+ * events kernels' reject without a load rests on it). */
+uint32_t pm_flat_short_gids(void* handle);
 void pm_flat_free(void* handle);
 
 #ifdef __cplusplus

@@ -15,6 +15,9 @@ interface:
                     scan (HipMatcher.read_batch_* / scan_batch_device)
     FlowTable       flow key -> carried state over the flow scan
                     (HipMatcher.read_flows_* / scan_flows_device)
+    unpack_events   (positions, gids) of the match list the events forms of
+                    both scans give (HipMatcher.read_*_events /
+                    scan_*_events_device)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401
@@ -23,11 +26,12 @@ from .matcher import (  # noqa: F401
     FlowTable,
     gen_stream,
     batch_offsets,
+    unpack_events,
     parse_line,
     KIND_RT,
     KIND_AC,
     KIND_AUTO,
 )
 
-__all__ = ["load", "Dictionary", "HipMatcher", "FlowTable", "gen_stream", "batch_offsets", "parse_line", "KIND_RT",
-           "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]
+__all__ = ["load", "Dictionary", "HipMatcher", "FlowTable", "gen_stream", "batch_offsets", "unpack_events", "parse_line",
+           "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]

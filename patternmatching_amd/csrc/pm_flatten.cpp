@@ -249,9 +249,13 @@ PmGidMap pm_assign_gids(const std::vector<std::string>& pats) {
         if (weight[a] != weight[b]) return weight[a] > weight[b];
         return pats[a].size() < pats[b].size();
     });
+    g.len.assign(1, 0);
+    g.len.reserve(P + 1);
     for (uint32_t k : order) {
         g.gid_of_index[k] = (uint32_t)g.index_of_gid.size();
         g.index_of_gid.push_back(k);
+        g.len.push_back((uint32_t)pats[k].size());
+        g.n_short += pats[k].size() <= 2;
     }
     return g;
 }

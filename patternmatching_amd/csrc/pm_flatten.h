@@ -77,6 +77,11 @@
 struct PmGidMap {
     std::vector<uint32_t> index_of_gid;  // [0] unused; gid -> pattern index (add order)
     std::vector<uint32_t> gid_of_index;  // pattern index -> gid
+    // the events kernels' filter (pm_kernels.h EvDev): len[gid] = the
+    // pattern's bytes ([0] = 0), and gids 1..n_short are exactly the patterns
+    // of <= 2 bytes
+    std::vector<uint32_t> len;
+    uint32_t n_short = 0;
 };
 
 struct RtImage {

@@ -126,6 +126,32 @@ hipError_t pm_launch_dfa_flows(const uint8_t* text, const int64_t* offsets, int6
                                const uint32_t* state_in, uint32_t* state_out, void* out, int outw,
                                unsigned long long* count, const DfaDev& t, uint32_t states, int64_t force_seg,
                                int num_cu, hipStream_t s);
+// The match list of an events launch (pm_hip.h): one u64 per event, position
+// << 24 | gid, for the positions whose answer g has len[g] >= min_len.  Each
+// event takes a slot from *cursor (atomicAdd, reserved in groups per wave)
+// and is stored only when the slot is below cap, so *cursor ends at its old
+// value plus every event found and nothing at or past events[cap] is
+// written; events may be null when cap is 0.  len: the bytes of every gid
+// ([0] = 0); n_short: gids 1..n_short are the patterns of <= 2 bytes
+// (pm_assign_gids), so min_len >= 3 rejects them with no load.
+struct EvDev {
+    uint64_t* events;
+    uint64_t cap;
+    unsigned long long* cursor;
+    const uint32_t* len;
+    uint32_t n_short;
+    uint32_t min_len;  // >= 1
+};
+// pm_launch_rt_batch with the match list as output (rt_batch_events_kernel);
+// text, offsets, the kernel forms and the memory safety are its own.
+hipError_t pm_launch_rt_batch_events(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                     const EvDev& ev, const RtDev& t, int num_cu, hipStream_t s);
+// pm_launch_dfa_flows with the match list as output (dfa_flow_events_kernel):
+// states, force_seg, the n == 0 copy pass and the memory safety are its own;
+// the segments are the count-only launch's (whole 16-position blocks).
+hipError_t pm_launch_dfa_flows_events(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                      const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
+                                      const DfaDev& t, uint32_t states, int64_t force_seg, int num_cu, hipStream_t s);
 // The sparse kernel (PmSparseKernel) a launch of this width runs, 0 when
 // it runs dense rows: the forced DfaDev::sparse_kernel where the object
 // and width allow it, else the product choice.

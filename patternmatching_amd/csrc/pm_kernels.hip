@@ -1814,6 +1814,305 @@ __global__ __launch_bounds__(DFA_THREADS) void dfa_flow_kernel(
     }
 }
 
+// ---- match list: events instead of dense ids --------------------------------
+// The events forms of the batched and the flow scan (pm_hip.h, "match
+// list"): the same walks, but a position's answer g is written only when its
+// pattern has at least min_len bytes, as one u64 event (position << 24 | g)
+// appended at a device cursor.  They are kernels of their own beside
+// rt_batch_kernel and dfa_flow_kernel, not further instantiations of them: a
+// template argument more would rename every existing instantiation, and
+// their code has to stay what it was.
+//
+// The filter (ev_keep): pm_assign_gids numbers the patterns of <= 2 bytes
+// first, so for min_len >= 3 a position is rejected by g <= n_short, with no
+// load; only a survivor reads the length table, and only when min_len > 3.
+//
+// The list.  Every event needs a slot from one u64 cursor that all waves
+// of the launch share, and one address takes about 90 returning atomics per
+// microsecond (MI355X_MICROARCH.md, dequeue).  A reservation per wave per
+// tile that holds an event is 51 k of them on 64 MiB of random ASCII under
+// snort at min_len 3 (one wave in 20 holds an event) and a million on the
+// lines stream.  Measured (the PM_EV_EAGER build below; snort, 100 KiB
+// streams, ms): batched ASCII 0.651 against 0.427 staged and 0.483 for the
+// dense ids, lines 12.8 against 4.19 and 4.23; flow ASCII 0.478 against
+// 0.280 and 0.362.  So a wave stages its events in LDS (EvWave: STAGE slots of its own, the
+// fill in a wave-uniform register -- no LDS atomics, no barriers) and
+// reserves once per flush: lane 0 adds the fill to the cursor, the old value
+// comes back through readfirstlane, and the lanes copy the staged events out
+// as contiguous 8-B stores, each only when its slot is below cap.  A step's
+// events are ranked by ballot + mbcnt (one event per lane) or by a wave prefix
+// sum of the lanes' counts (the flow kernel's 16 positions per lane); a step
+// with more events than STAGE reserves for itself and stores directly.
+// PM_EV_EAGER 1 (ablation build) makes every step do that: the
+// reservation per wave per step, for the A/B in profiles/events/.
+// All of it -- ballot, readfirstlane, DPP, the cross-lane LDS copy -- is
+// valid only with all 64 lanes active: the callers reach ev_reserve / ev_flush
+// from wave-uniform control flow only.
+#ifndef PM_EV_EAGER
+#define PM_EV_EAGER 0
+#endif
+template <int STAGE>
+struct EvWave {
+    uint64_t* buf;   // this wave's STAGE slots of LDS
+    uint32_t fill;   // staged events (wave-uniform)
+};
+struct EvSlot {      // where a step's events go (wave-uniform)
+    bool direct;
+    uint32_t lds;
+    unsigned long long glob;
+};
+
+__device__ __forceinline__ bool ev_keep(uint32_t g, const EvDev& ev) {
+    if (ev.min_len >= 3) {
+        bool keep = g > ev.n_short;
+        if (ev.min_len > 3 && keep) keep = ev.len[g] >= ev.min_len;
+        return keep;
+    }
+    return g != 0u && (ev.min_len <= 1 || ev.len[g] >= ev.min_len);
+}
+
+// `count` slots at the cursor (all lanes active; count wave-uniform, > 0).
+__device__ __forceinline__ unsigned long long ev_claim(uint32_t count, const EvDev& ev) {
+    unsigned long long b = 0;
+    if ((threadIdx.x & 63) == 0) b = atomicAdd(ev.cursor, (unsigned long long)count);
+    return rfl64(b);
+}
+
+template <int STAGE>
+__device__ __forceinline__ void ev_flush(EvWave<STAGE>& w, const EvDev& ev) {
+    if (w.fill == 0) return;
+    // the staged events were written by other lanes of this wave
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const unsigned long long b = ev_claim(w.fill, ev);
+    for (uint32_t k = threadIdx.x & 63; k < w.fill; k += 64)
+        if (b + k < ev.cap) ev.events[b + k] = w.buf[k];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    w.fill = 0;
+}
+
+// Room for the `total` events of one step of this wave (wave-uniform, > 0).
+template <int STAGE>
+__device__ __forceinline__ EvSlot ev_reserve(EvWave<STAGE>& w, uint32_t total, const EvDev& ev) {
+    EvSlot r{PM_EV_EAGER || total > (uint32_t)STAGE, 0u, 0ull};
+    if (r.direct) {
+        r.glob = ev_claim(total, ev);
+    } else {
+        if (w.fill + total > (uint32_t)STAGE) ev_flush(w, ev);
+        r.lds = w.fill;
+        w.fill += total;
+    }
+    return r;
+}
+
+// Event number k of the step (the lane's rank among the step's events).
+template <int STAGE>
+__device__ __forceinline__ void ev_put(const EvWave<STAGE>& w, const EvSlot& r, uint32_t k, uint64_t e,
+                                       const EvDev& ev) {
+    if (r.direct) {
+        if (r.glob + k < ev.cap) ev.events[r.glob + k] = e;
+    } else {
+        w.buf[r.lds + k] = e;
+    }
+}
+
+constexpr int PM_EV_GID_BITS = 24;  // pm_hip.h: event = position << 24 | gid
+
+// rt_batch_kernel's tiles, starts and walk (its comment above holds word for
+// word: the offsets' search per workgroup, the LDS mask of the streams that
+// begin inside a tile, the clamps that keep every read in text[0, i]); lane k
+// owns position base + k, and after the walk the wave's kept answers are
+// ranked by ballot + mbcnt and staged.  128 slots per wave: 16 KiB beside the
+// 128 KiB of t12.
+constexpr int RT_EV_STAGE = 128;
+template <bool SMALL>
+__global__ __launch_bounds__(RT_THREADS) void rt_batch_events_kernel(const uint8_t* __restrict__ text,
+                                                                     const int64_t* __restrict__ offs, int64_t nseg,
+                                                                     int64_t n, EvDev ev, RtDev t) {
+    constexpr int kT12Words = SMALL ? 0 : RT_T2_U16 / 2;
+    constexpr int kStageWords = (RT_THREADS / 64) * RT_EV_STAGE * 2;
+    __shared__ __attribute__((aligned(16))) uint32_t s_lds[kT12Words + kStageWords + RT_BATCH_TILE / 32];
+    uint32_t* const s_mask = s_lds + kT12Words + kStageWords;
+    const uint16_t* s_t = t.t12;
+    const int tid = threadIdx.x;
+    EvWave<RT_EV_STAGE> stage{reinterpret_cast<uint64_t*>(s_lds + kT12Words) + (tid >> 6) * RT_EV_STAGE, 0u};
+    if (!SMALL) {
+        const uint4* src = reinterpret_cast<const uint4*>(t.t12);
+        uint4* dst = reinterpret_cast<uint4*>(s_lds);
+        for (int k = tid; k < RT_T2_U16 * 2 / 16; k += RT_THREADS) dst[k] = src[k];
+        __syncthreads();
+        s_t = reinterpret_cast<const uint16_t*>(s_lds);
+    }
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t T0 = ntiles * (int64_t)blockIdx.x / (int64_t)gridDim.x;
+    const int64_t T1 = ntiles * ((int64_t)blockIdx.x + 1) / (int64_t)gridDim.x;
+    const int64_t noffs = nseg + 1;
+    int64_t a = batch_seek(offs, 0, noffs, T0 * RT_BATCH_TILE + 1);
+    for (int64_t T = T0; T < T1; ++T) {
+        const int64_t base = T * RT_BATCH_TILE;
+        const int64_t end = base + RT_BATCH_TILE < n ? base + RT_BATCH_TILE : n;
+        a = batch_seek(offs, a, noffs, base + 1);
+        const int64_t b = batch_seek(offs, a, noffs, end);
+        int64_t start = a > 0 ? (int64_t)rfl64((uint64_t)offs[a - 1]) : 0;
+        if (b > a) {  // workgroup-uniform
+            __syncthreads();
+            if (tid < RT_BATCH_TILE / 32) s_mask[tid] = 0u;
+            __syncthreads();
+            for (int64_t j = a + tid; j < b; j += RT_THREADS) {
+                const int64_t rel = offs[j] - base;
+                if (rel > 0 && rel < RT_BATCH_TILE) atomicOr(&s_mask[rel >> 5], 1u << (rel & 31));
+            }
+            __syncthreads();
+            int w = tid >> 5;
+            uint32_t m = s_mask[w] & (0xFFFFFFFFu >> (31 - (tid & 31)));
+            while (!m && w > 0) m = s_mask[--w];
+            if (m) start = base + w * 32 + 31 - __clz(m);
+        }
+        const int64_t i = base + tid;
+        uint32_t v = 0;
+        if (i < n) {
+            start = start < 0 ? 0 : start > i ? i : start;
+            v = rt_one(text, s_t, t, i, start);
+        }
+        // all 64 lanes of every wave are here (a lane past n holds v = 0)
+        const bool keep = ev_keep(v, ev);
+        const uint64_t km = __ballot(keep);
+        if (km) {
+            const EvSlot slot = ev_reserve(stage, (uint32_t)__popcll(km), ev);
+            if (keep) ev_put(stage, slot, wave_prefix(km), (uint64_t)i << PM_EV_GID_BITS | v, ev);
+        }
+        a = b;
+    }
+    ev_flush(stage, ev);
+}
+
+// dfa_flow_kernel's walk (its comment above holds for the segments, the
+// seeks, the warm-ups, the states in and out, the empty streams' copy pass
+// and the memory safety; no id is stored), restructured so that the events
+// of a wave can be ranked and staged together.  Of the two ways to aggregate
+// them -- one global reservation per wave-uniform step, or staging per wave
+// in LDS with one reservation per flush -- this is the second, on top of the
+// wave-uniform steps the first needs as well: a reservation per step is
+// still 36 k atomics on one address on 64 MiB of ASCII (a wave's step covers
+// 1,024 positions, and every second one holds an event) and measured 1.3-1.5x
+// the dense id call there (the figures above); staged, it is one per 256
+// events, and the call takes 0.77-0.87x the id call's time on ASCII and
+// 0.98-1.08x on the lines stream (scripts/bench_events.py, profiles/events/).
+// The id form's loops are per lane (`for sg`, `while (i < hi)`); here both are
+// wave-uniform: every lane of a wave runs the outer loop as often as the
+// wave's first lane, and the step loop while any lane has positions left, so
+// all 64 lanes reach the end of every step together -- a lane without a
+// segment, or past its end, takes no step and brings no events; a lane on a
+// byte-wise step brings at most one, a lane on a 16-position block up to 16.
+// Per step: r[q] = the kept gid of position p0 + q (bit q of `keep`), the
+// lanes' counts go through wave_scan_incl, and the lanes put their events at
+// consecutive ranks.  CODED: an inline code is its gid, so codes <= n_short
+// drop with no lookup; DFA_ESC fetches outt[state] as the id form does.
+constexpr int DFA_EV_STAGE = 256;
+template <bool CODED>
+__global__ __launch_bounds__(DFA_THREADS) void dfa_flow_events_kernel(
+    const uint8_t* __restrict__ text, const int64_t* __restrict__ offs, int64_t nseg, int64_t n,
+    const uint32_t* __restrict__ state_in, uint32_t* __restrict__ state_out, EvDev ev,
+    const uint32_t* __restrict__ nxt, const uint32_t* __restrict__ outt, uint32_t states, int64_t warm,
+    int64_t seg_len, const uint32_t* __restrict__ gram3) {
+    __shared__ uint64_t s_stage[(DFA_THREADS / 64) * DFA_EV_STAGE];
+    EvWave<DFA_EV_STAGE> stage{s_stage + (threadIdx.x >> 6) * DFA_EV_STAGE, 0u};
+    const int64_t nlane = (n + seg_len - 1) / seg_len;
+    const int64_t stride = (int64_t)gridDim.x * DFA_THREADS;
+    const int64_t gtid = (int64_t)blockIdx.x * DFA_THREADS + threadIdx.x;
+    const int64_t noffs = nseg + 1;
+    auto load_state = [&](int64_t j) -> uint32_t {  // j in [0, nseg)
+        const uint32_t s = state_in ? state_in[j] : 0u;
+        return s < states ? s : 0u;
+    };
+    for (int64_t sg0 = gtid - (threadIdx.x & 63); sg0 < nlane; sg0 += stride) {  // wave-uniform
+        const int64_t sg = sg0 + (threadIdx.x & 63);
+        int64_t i = 0, hi = 0, end = 0, j = 0;  // a lane without a segment: no step
+        uint32_t s = 0;
+        if (sg < nlane) {
+            const int64_t lo = sg * seg_len;
+            hi = lo + seg_len < n ? lo + seg_len : n;
+            // the stream holding lo: the first offset > lo, minus one
+            j = flow_seek(offs, 0, noffs, lo + 1) - 1;
+            j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+            int64_t start = offs[j];
+            start = start < 0 ? 0 : start > lo ? lo : start;
+            end = offs[j + 1];
+            int64_t wlo = lo - warm;
+            if (wlo < start) wlo = start;
+            int64_t w = wlo;
+            if (gram3) w = dfa_sync_lo(text, lo, wlo, gram3);  // in [wlo, lo]: never before start
+            s = (w == wlo && wlo == start) ? load_state(j) : 0u;
+            for (int64_t k = w; k < lo; ++k) {
+                const uint32_t v = nxt[(size_t)s * 256 + text[k]];
+                s = CODED ? v & DFA_STATE_MASK : v;
+            }
+            i = lo;
+        }
+        while (__any(i < hi)) {  // wave-uniform: one step of every lane that has positions left
+            const int64_t p0 = i;
+            uint32_t r[16];
+            uint32_t keep = 0;  // bit q: position p0 + q is an event, its gid r[q]
+            if (i < hi) {
+                if ((i & 15) == 0 && i + 16 <= hi && i + 16 <= end) {
+                    const uint4 tw = *reinterpret_cast<const uint4*>(text + i);
+                    const uint32_t W[4] = {tw.x, tw.y, tw.z, tw.w};
+                    uint32_t st[16];
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const uint32_t v = nxt[(size_t)s * 256 + ((W[q >> 2] >> (8 * (q & 3))) & 0xFFu)];
+                        s = CODED ? v & DFA_STATE_MASK : v;
+                        r[q] = CODED ? v >> 20 : 0u;
+                        st[q] = s;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        if (CODED) r[q] = r[q] == DFA_ESC ? outt[st[q]] : r[q];
+                        else r[q] = outt[st[q]];
+                        keep |= (uint32_t)ev_keep(r[q], ev) << q;
+                    }
+                    i += 16;
+                } else {
+                    const uint32_t v = nxt[(size_t)s * 256 + text[i]];
+                    s = CODED ? v & DFA_STATE_MASK : v;
+                    uint32_t id = CODED ? v >> 20 : outt[s];
+                    if (CODED && id == DFA_ESC) id = outt[s];
+                    r[0] = id;
+                    keep = (uint32_t)ev_keep(id, ev);
+                    ++i;
+                }
+                if (i == end) {  // position end - 1 was stream j's last byte
+                    if (state_out) state_out[j] = s;
+                    if (i < hi) {
+                        // the next stream that is not empty: the first offset > i, minus one
+                        j = flow_seek(offs, j + 2 < noffs ? j + 2 : noffs, noffs, i + 1) - 1;
+                        j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+                        end = offs[j + 1];
+                        s = load_state(j);
+                    }
+                }
+            }
+            // all 64 lanes are here
+            if (__any(keep != 0u)) {
+                const uint32_t c = __popc(keep);
+                const uint32_t incl = wave_scan_incl(c);
+                const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
+                const EvSlot slot = ev_reserve(stage, total, ev);
+                uint32_t k = incl - c;
+#pragma unroll
+                for (int q = 0; q < 16; ++q)
+                    if ((keep >> q) & 1u)
+                        ev_put(stage, slot, k++, (uint64_t)(p0 + q) << PM_EV_GID_BITS | r[q], ev);
+            }
+        }
+    }
+    ev_flush(stage, ev);
+    if (state_out)  // empty streams keep their state (as used: an invalid one is the root)
+        for (int64_t j = gtid; j < nseg; j += stride)
+            if (offs[j + 1] <= offs[j]) state_out[j] = load_state(j);
+}
+
 // The sparse (default-transition) form, pm_flatten.h: rows only for the
 // states whose row differs from their fallback's in more than PM_SDFA_K
 // bytes, 16-B records for the rest (8-B units in pm_pack_sparse8's
@@ -3056,6 +3355,21 @@ hipError_t pm_launch_rt_batch(const uint8_t* text, const int64_t* offsets, int64
     return hipGetLastError();
 }
 
+// Its events form (rt_batch_events_kernel): the same two kernel forms.
+hipError_t pm_launch_rt_batch_events(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                     const EvDev& ev, const RtDev& t, int num_cu, hipStream_t s) {
+    if (n <= 0 || nseg <= 0) return hipSuccess;
+    if (!text || !offsets || num_cu <= 0) return hipErrorInvalidValue;
+    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap)) return hipErrorInvalidValue;
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
+    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
+    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    if (small) hipLaunchKernelGGL(rt_batch_events_kernel<true>, g, b, 0, s, text, offsets, nseg, n, ev, t);
+    else hipLaunchKernelGGL(rt_batch_events_kernel<false>, g, b, 0, s, text, offsets, nseg, n, ev, t);
+    return hipGetLastError();
+}
+
 hipError_t pm_launch_rt_serve(PmServeReq* req, uint64_t* fwd, uint32_t* done, int blocks, uint64_t seen,
                               uint64_t gen, int64_t idle_ticks, const RtDev& t, hipStream_t s) {
     if (blocks <= 0) return hipErrorInvalidValue;
@@ -3239,6 +3553,24 @@ hipError_t pm_launch_dfa(const uint8_t* text, int64_t stream_start, int64_t pos0
 // x 2 chains), none shorter than short_seg, whole 16-position blocks (32 with
 // ids) -- or force_seg (the "flow_seg" option) when it is not 0.  With n == 0
 // only the empty streams' state copy runs.  No scratch, nothing allocated.
+// The segment length and the grid of a flow launch; false when the grid is
+// past what a launch takes.
+static bool flow_shape(int64_t nseg, int64_t n, int64_t align, int64_t force_seg, int num_cu, int64_t& seg,
+                       int64_t& blocks) {
+    const int64_t lanes = (int64_t)num_cu * DFA_LANES_PER_CU * DFA_CHAINS;
+    seg = (n + lanes - 1) / lanes;
+    const int64_t short_seg = std::min<int64_t>(512, std::max<int64_t>(n < (1 << 20) ? PM_DFA_SMALL_SEG : 64, n >> 16));
+    if (seg < short_seg) seg = short_seg;
+    seg = (seg + align - 1) / align * align;
+    if (force_seg) seg = force_seg;
+    const int64_t nlane = (n + seg - 1) / seg;
+    // (n == 0: the copy pass alone, a lane per stream up to one workgroup per CU)
+    blocks = n > 0 ? (nlane + DFA_THREADS - 1) / DFA_THREADS
+                   : std::min<int64_t>((nseg + DFA_THREADS - 1) / DFA_THREADS, num_cu);
+    if (blocks < 1) blocks = 1;
+    return blocks <= (int64_t)1 << 30;
+}
+
 hipError_t pm_launch_dfa_flows(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
                                const uint32_t* state_in, uint32_t* state_out, void* out, int outw,
                                unsigned long long* count, const DfaDev& t, uint32_t states, int64_t force_seg,
@@ -3248,19 +3580,9 @@ hipError_t pm_launch_dfa_flows(const uint8_t* text, const int64_t* offsets, int6
     if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
     if (!out) outw = 0;
     if (outw != 0 && outw != 2 && outw != 4) return hipErrorInvalidValue;
-    const int64_t lanes = (int64_t)num_cu * DFA_LANES_PER_CU * DFA_CHAINS;
-    int64_t seg = (n + lanes - 1) / lanes;
-    const int64_t short_seg = std::min<int64_t>(512, std::max<int64_t>(n < (1 << 20) ? PM_DFA_SMALL_SEG : 64, n >> 16));
-    if (seg < short_seg) seg = short_seg;
-    const int64_t align = outw != 0 ? DFA_DENSE_BLK : 16;
-    seg = (seg + align - 1) / align * align;
-    if (force_seg) seg = force_seg;
-    const int64_t nlane = (n + seg - 1) / seg;
-    // (n == 0: the copy pass alone, a lane per stream up to one workgroup per CU)
-    int64_t blocks = n > 0 ? (nlane + DFA_THREADS - 1) / DFA_THREADS
-                           : std::min<int64_t>((nseg + DFA_THREADS - 1) / DFA_THREADS, num_cu);
-    if (blocks < 1) blocks = 1;
-    if (blocks > (int64_t)1 << 30) return hipErrorInvalidValue;
+    int64_t seg, blocks;
+    if (!flow_shape(nseg, n, outw != 0 ? DFA_DENSE_BLK : 16, force_seg, num_cu, seg, blocks))
+        return hipErrorInvalidValue;
     const dim3 g((unsigned)blocks), b(DFA_THREADS);
     const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
 #define PM_FLOW_LAUNCH(W_, C_)                                                                                      \
@@ -3276,6 +3598,28 @@ hipError_t pm_launch_dfa_flows(const uint8_t* text, const int64_t* offsets, int6
         else PM_FLOW_LAUNCH(0, false);
     }
 #undef PM_FLOW_LAUNCH
+    return hipGetLastError();
+}
+
+// The flow scan's events form (dfa_flow_events_kernel): the count-only
+// launch's segments (no id stores to align to lines).
+hipError_t pm_launch_dfa_flows_events(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                      const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
+                                      const DfaDev& t, uint32_t states, int64_t force_seg, int num_cu, hipStream_t s) {
+    if (nseg <= 0 || n < 0 || (n == 0 && !state_out)) return hipSuccess;
+    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
+    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap)) return hipErrorInvalidValue;
+    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
+    int64_t seg, blocks;
+    if (!flow_shape(nseg, n, 16, force_seg, num_cu, seg, blocks)) return hipErrorInvalidValue;
+    const dim3 g((unsigned)blocks), b(DFA_THREADS);
+    const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
+    if (t.coded)
+        hipLaunchKernelGGL(dfa_flow_events_kernel<true>, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev,
+                           t.next, t.out, states, t.warm, seg, g3);
+    else
+        hipLaunchKernelGGL(dfa_flow_events_kernel<false>, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev,
+                           t.next, t.out, states, t.warm, seg, g3);
     return hipGetLastError();
 }
 

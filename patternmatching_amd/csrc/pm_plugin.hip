@@ -254,6 +254,10 @@ struct BatchStage {
     uint32_t* d_st_in = nullptr;
     uint32_t* d_st_out = nullptr;
     size_t cap_st = 0;
+    // the events calls' list and its cursor (pm_hip_read_*_events), cap_ev events
+    uint64_t* d_ev = nullptr;
+    unsigned long long* d_nev = nullptr;
+    size_t cap_ev = 0;
     hipStream_t s = nullptr;
 };
 struct PmHip {
@@ -271,6 +275,7 @@ struct PmHip {
     DfaDev dfa{};
     const uint32_t* d_parent = nullptr;  // PmParents, gid space (scoring)
     const uint32_t* d_depth = nullptr;
+    const uint32_t* d_len = nullptr;  // PmGidMap::len (the events kernels' filter)
     std::vector<uint32_t> parent;
     std::string cache_dir;   // compiled-image cache (else $PM_IMAGE_CACHE)
     bool cache_hit = false;
@@ -310,6 +315,7 @@ struct PmHip {
     BatchStage batch;
     uint32_t dfa_states = 0;  // states of the DFA image on the device (0: none); pm_hip_flow_states
     int64_t flow_seg = 0;     // option "flow_seg": the flow scan's lane segment (0: the launcher's choice)
+    int64_t events_cap = 0;   // option "events_cap": the host events forms' first device capacity (0: the default)
 };
 
 // Drop the pick's choice and measurements (a measurement still in flight
@@ -1300,6 +1306,7 @@ void pm_hip_compile(void* obj) {
     o->d_parent = (const uint32_t*)dalloc_copy(o, im.par.parent.data(), im.par.parent.size() * 4);
     o->d_depth = (const uint32_t*)dalloc_copy(o, im.par.depth.data(), im.par.depth.size() * 4);
     o->parent = std::move(im.par.parent);
+    o->d_len = (const uint32_t*)dalloc_copy(o, o->gids.len.data(), o->gids.len.size() * 4);
     o->id_of_gid.assign(o->gids.index_of_gid.size(), PM_NULL_PATTERN_ID);
     for (size_t g = 1; g < o->gids.index_of_gid.size(); ++g) o->id_of_gid[g] = o->ids[o->gids.index_of_gid[g]];
     o->compiled = true;
@@ -1373,6 +1380,8 @@ void pm_hip_free(void* obj) {
     if (o->batch.d_offs) (void)hipFree(o->batch.d_offs);
     if (o->batch.d_st_in) (void)hipFree(o->batch.d_st_in);
     if (o->batch.d_st_out) (void)hipFree(o->batch.d_st_out);
+    if (o->batch.d_ev) (void)hipFree(o->batch.d_ev);
+    if (o->batch.d_nev) (void)hipFree(o->batch.d_nev);
     if (o->batch.s) (void)hipStreamDestroy(o->batch.s);
     free_pick(o->pick);
     for (PipeSlot& q : o->slot) {
@@ -1744,6 +1753,200 @@ int pm_hip_read_flows(void* obj, const char* buf, const int64_t* offsets, size_t
     return read_flows(as(obj), reinterpret_cast<const uint8_t*>(buf), offsets, nseg, state, nullptr, out);
 }
 
+// ---- match list: the events forms of the batched and the flow scan ---------
+constexpr int PM_EVENT_GID_BITS = 24;  // event = position << 24 | gid
+constexpr int64_t PM_EVENT_MAX_N = (int64_t)1 << 40;
+
+// What the events forms add to their dense siblings' arguments: 0, or -2.
+static int events_args_check(int64_t n, uint32_t min_len, const uint64_t* events, uint64_t cap, const void* nevents,
+                             bool device) {
+    if (n > PM_EVENT_MAX_N || min_len < 1 || !nevents || (!events && cap) ||
+        (device && (((uintptr_t)events & 7) || ((uintptr_t)nevents & 7)))) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (n <= 2^40, min_len >= 1, nevents required, events 8-B aligned and NULL only with "
+                      "cap == 0)");
+        return -2;
+    }
+    return 0;
+}
+
+// -4 when a gid does not fit an event's low 24 bits.
+static int events_gid_check(PmHip* o) {
+    if (o->gids.index_of_gid.size() > ((size_t)1 << PM_EVENT_GID_BITS)) {
+        std::snprintf(g_err, sizeof(g_err), "events need fewer than 2^24 patterns (have %zu)",
+                      o->gids.index_of_gid.size() - 1);
+        return -4;
+    }
+    return 0;
+}
+
+static EvDev events_dev(PmHip* o, uint32_t min_len, uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents) {
+    return EvDev{d_events, cap, d_nevents, o->d_len, o->gids.n_short, min_len};
+}
+
+int pm_hip_scan_batch_events_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, uint32_t min_len, uint64_t* d_events, uint64_t cap,
+                                    unsigned long long* d_nevents, void* hip_stream) {
+    PmHip* o = as(obj);
+    if (const int rc = batch_check(o)) return rc;
+    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) ||
+        (nseg > 0 && n > 0 && (!d_text || !d_offsets))) {
+        std::snprintf(g_err, sizeof(g_err), "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned)");
+        return -2;
+    }
+    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
+    if (const int rc = events_gid_check(o)) return rc;
+    if (nseg == 0 || n == 0) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess)
+        e = pm_launch_rt_batch_events(d_text, d_offsets, nseg, n, events_dev(o, min_len, d_events, cap, d_nevents),
+                                      o->rt, o->num_cu, (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "batch events launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_RT;
+    o->last_form = 0;
+    return 0;
+}
+
+int pm_hip_scan_flows_events_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t min_len,
+                                    uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                    void* hip_stream) {
+    PmHip* o = as(obj);
+    if (const int rc = flows_check(o)) return rc;
+    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_state_in & 3) ||
+        ((uintptr_t)d_state_out & 3) || (d_state_in && d_state_in == d_state_out) ||
+        (nseg > 0 && (!d_offsets || (n > 0 && !d_text)))) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned, states 4-B aligned, "
+                      "state_in != state_out)");
+        return -2;
+    }
+    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
+    if (const int rc = events_gid_check(o)) return rc;
+    if (nseg == 0 || (n == 0 && !d_state_out)) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess)
+        e = pm_launch_dfa_flows_events(d_text, d_offsets, nseg, n, d_state_in, d_state_out,
+                                       events_dev(o, min_len, d_events, cap, d_nevents), o->dfa, o->dfa_states,
+                                       o->flow_seg, o->num_cu, (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "flow events launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_AC;
+    o->last_form = 1;
+    return 0;
+}
+
+uint32_t pm_hip_pattern_len(void* obj, uint32_t gid) {
+    PmHip* o = as(obj);
+    return gid < o->gids.len.size() ? o->gids.len[gid] : 0u;
+}
+
+// The host forms: text, offsets (and states) to the batch staging, an events
+// launch into the staging's list, the count back; a list that did not hold
+// every event is grown to the count and the launch repeated from the same
+// inputs (the states come in through d_st_in and leave through d_st_out, so
+// the first launch changed nothing the second reads).  Then only the events
+// come back, are sorted, and the first min(cap, total) handed over.
+// Everything is checked before anything is written.
+static int read_events(PmHip* o, bool flows, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                       uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents) {
+    if (const int rc = flows ? flows_check(o) : batch_check(o)) return rc;
+    bool ok = (nseg == 0 || offsets) && nseg < ((size_t)1 << 60);
+    if (ok && nseg) {
+        ok = offsets[0] == 0;
+        for (size_t j = 0; ok && j < nseg; ++j) ok = offsets[j] <= offsets[j + 1];
+        if (ok && offsets[nseg] > 0) ok = buf != nullptr;
+        if (ok && flows && state)
+            for (size_t j = 0; ok && j < nseg; ++j) ok = state[j] < o->dfa_states;
+    }
+    if (!ok) {
+        std::snprintf(g_err, sizeof(g_err), "bad arguments (offsets[0] == 0, offsets non-decreasing%s)",
+                      flows ? ", every state below pm_hip_flow_states" : "");
+        return -2;
+    }
+    const size_t n = nseg ? (size_t)offsets[nseg] : 0;
+    if (const int rc = events_args_check((int64_t)std::min<size_t>(n, (size_t)PM_EVENT_MAX_N + 1), min_len, events, cap,
+                                         nevents, false))
+        return rc;
+    if (const int rc = events_gid_check(o)) return rc;
+    *nevents = 0;
+    if (n == 0) return 0;  // the flow form: every stream keeps its state, which the caller's array holds
+    PM_CHECK(hipSetDevice(o->device));
+    BatchStage& q = o->batch;
+    batch_stage_grow(q, n, nseg);
+    const bool st = flows && state;
+    if (st && nseg > q.cap_st) {
+        if (q.d_st_in) PM_CHECK(hipFree(q.d_st_in));
+        if (q.d_st_out) PM_CHECK(hipFree(q.d_st_out));
+        q.d_st_in = q.d_st_out = nullptr;
+        q.cap_st = 0;
+        const size_t c = std::max(nseg, (size_t)1 << 10);
+        PM_CHECK(hipMalloc(&q.d_st_in, c * sizeof(uint32_t)));
+        PM_CHECK(hipMalloc(&q.d_st_out, c * sizeof(uint32_t)));
+        q.cap_st = c;
+    }
+    if (!q.d_nev) PM_CHECK(hipMalloc(&q.d_nev, sizeof(unsigned long long)));
+    serve_stop(o);  // a device launch wants the whole device
+    PM_CHECK(hipMemcpyAsync(q.d_text, buf, n, hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
+    if (st) PM_CHECK(hipMemcpyAsync(q.d_st_in, state, nseg * sizeof(uint32_t), hipMemcpyHostToDevice, q.s));
+    size_t dcap = o->events_cap > 0 ? (size_t)o->events_cap : std::max<size_t>(1024, n / 16);
+    unsigned long long total = 0;
+    for (int launch = 0; launch < 2; ++launch) {
+        if (dcap > q.cap_ev) {
+            PM_CHECK(hipStreamSynchronize(q.s));
+            if (q.d_ev) PM_CHECK(hipFree(q.d_ev));
+            q.d_ev = nullptr;
+            q.cap_ev = 0;
+            PM_CHECK(hipMalloc(&q.d_ev, dcap * sizeof(uint64_t)));
+            q.cap_ev = dcap;
+        }
+        PM_CHECK(hipMemsetAsync(q.d_nev, 0, sizeof(unsigned long long), q.s));
+        const EvDev ev = events_dev(o, min_len, q.d_ev, dcap, q.d_nev);
+        const hipError_t e =
+            flows ? pm_launch_dfa_flows_events(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, st ? q.d_st_in : nullptr,
+                                               st ? q.d_st_out : nullptr, ev, o->dfa, o->dfa_states, o->flow_seg,
+                                               o->num_cu, q.s)
+                  : pm_launch_rt_batch_events(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, o->rt, o->num_cu, q.s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(q.s);
+            std::snprintf(g_err, sizeof(g_err), "%s events launch: %s", flows ? "flow" : "batch", hipGetErrorString(e));
+            return -3;
+        }
+        PM_CHECK(hipMemcpyAsync(&total, q.d_nev, sizeof(total), hipMemcpyDeviceToHost, q.s));
+        PM_CHECK(hipStreamSynchronize(q.s));
+        if (total <= dcap) break;
+        dcap = (size_t)total;  // the list was cut short: once more, with room for every event
+    }
+    o->last_kernel = flows ? KIND_AC : KIND_RT;
+    o->last_form = flows ? 1 : 0;
+    std::vector<uint64_t> ev((size_t)total);
+    if (total) PM_CHECK(hipMemcpyAsync(ev.data(), q.d_ev, ev.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    if (st) PM_CHECK(hipMemcpyAsync(state, q.d_st_out, nseg * sizeof(uint32_t), hipMemcpyDeviceToHost, q.s));
+    PM_CHECK(hipStreamSynchronize(q.s));
+    std::sort(ev.begin(), ev.end());  // position order: the position is the high bits, one event per position
+    if (cap && total) std::memcpy(events, ev.data(), std::min<size_t>(cap, ev.size()) * sizeof(uint64_t));
+    *nevents = (size_t)total;
+    return 0;
+}
+
+int pm_hip_read_batch_events(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t min_len,
+                             uint64_t* events, size_t cap, size_t* nevents) {
+    return read_events(as(obj), false, buf, offsets, nseg, nullptr, min_len, events, cap, nevents);
+}
+
+int pm_hip_read_flows_events(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                             uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents) {
+    return read_events(as(obj), true, buf, offsets, nseg, state, min_len, events, cap, nevents);
+}
+
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,
                         unsigned long long* d_counts, void* hip_stream) {
     PmHip* o = as(obj);
@@ -1799,6 +2002,7 @@ size_t pm_hip_scratch_bytes(void* obj) {
     if (o->batch.d_text) b += o->batch.cap_n + 16 + o->batch.cap_n * sizeof(uint32_t);
     if (o->batch.d_offs) b += o->batch.cap_offs * sizeof(int64_t);
     if (o->batch.d_st_in) b += 2 * o->batch.cap_st * sizeof(uint32_t);
+    if (o->batch.d_ev) b += o->batch.cap_ev * sizeof(uint64_t) + sizeof(unsigned long long);
     return b;
 }
 
@@ -1903,6 +2107,11 @@ int pm_hip_set_option(void* obj, const char* name, int64_t value) {
     if (k == "flow_seg") {  // the flow scan's lane segment (tests, A/B timing)
         if (value != 0 && (value < 16 || value > 4096 || value % 16)) return -1;
         o->flow_seg = value;
+        return 0;
+    }
+    if (k == "events_cap") {  // the host events forms' first device capacity (tests force the second launch)
+        if (value < 0) return -1;
+        o->events_cap = value;
         return 0;
     }
     if (k == "rt_small_max") {
@@ -2106,6 +2315,7 @@ size_t pm_flat_array(void* handle, const char* name, const void** data, size_t* 
         return ret(h->flinfo);
     }
     if (s == "index_of_gid") return ret(h->g.index_of_gid);
+    if (s == "len") return ret(h->g.len);
     if (s == "parent") return ret(h->par.parent);
     if (s == "depth") return ret(h->par.depth);
     *data = nullptr;
@@ -2167,6 +2377,8 @@ uint32_t pm_flat_flow_states(void* handle) {
     PmFlatHandle* h = static_cast<PmFlatHandle*>(handle);
     return h->kind == 2 && !h->dfa.next.empty() ? h->dfa.states : 0u;
 }
+
+uint32_t pm_flat_short_gids(void* handle) { return static_cast<PmFlatHandle*>(handle)->g.n_short; }
 
 void pm_flat_free(void* handle) { delete static_cast<PmFlatHandle*>(handle); }
 

@@ -121,6 +121,24 @@ def batch_offsets(buffers) -> np.ndarray:
     return offs
 
 
+EVENT_GID_BITS = 24
+
+
+def unpack_events(ev):
+    """(positions int64, gids uint32) of an array of match events
+    (include/pm_hip.h: one u64 per event, position << 24 | gid)."""
+    ev = np.ascontiguousarray(ev, dtype=np.uint64)
+    return ((ev >> np.uint64(EVENT_GID_BITS)).astype(np.int64),
+            (ev & np.uint64((1 << EVENT_GID_BITS) - 1)).astype(np.uint32))
+
+
+def _split_events(pos, codes, offs):
+    """Events of a batched buffer -> per stream (positions relative to the
+    stream, codes); pos ascending."""
+    cut = np.searchsorted(pos, offs)
+    return [(pos[cut[j]:cut[j + 1]] - offs[j], codes[cut[j]:cut[j + 1]]) for j in range(len(offs) - 1)]
+
+
 class FlowTable:
     """The carried states of many live flows over one matcher (ac / auto
     kinds): a dict of flow key -> flow state, and one flow call
@@ -157,6 +175,29 @@ class FlowTable:
         for k, s in zip(keys, state.tolist()):
             self.states[k] = s
         return [codes[offs[j]:offs[j + 1]] for j in range(len(packets))]
+
+    def scan_events(self, packets, min_len=3):
+        """scan() with the match list instead of dense codes: per packet, in
+        order, (positions inside the packet, codes) of the positions where a
+        pattern of at least min_len bytes ends (HipMatcher.read_flows_events).
+        The flows' states advance exactly as in scan()."""
+        keys = [k for k, _ in packets]
+        if len(set(keys)) != len(keys):
+            seen = set()
+            dup = next(k for k in keys if k in seen or seen.add(k))
+            raise ValueError(f"flow {dup!r} appears twice in one scan_events(): concatenate its packets")
+        if not packets:
+            return []
+        bufs = [b for _, b in packets]
+        offs = batch_offsets(bufs)
+        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in bufs]
+        data = np.concatenate(parts)
+        state = np.array([self.states.get(k, 0) for k in keys], dtype=np.uint32)
+        pos, codes, state = self.matcher.read_flows_events(data, offs, state, min_len)
+        for k, s in zip(keys, state.tolist()):
+            self.states[k] = s
+        return _split_events(pos, codes, offs)
 
     def end(self, key):
         """Forget a flow: its key, seen again, starts a fresh one."""
@@ -341,6 +382,90 @@ class HipMatcher:
         data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
         codes = self.read_batch_codes(data, offs)
         return [codes[offs[j]:offs[j + 1]] for j in range(len(buffers))]
+
+    # --- match list: events instead of dense ids (batched and flow scans) --
+    def pattern_len(self, gid):
+        """pm_hip_pattern_len: the bytes of pattern gid (0 out of range)."""
+        return self.lib.pm_hip_pattern_len(self.obj, gid)
+
+    def scan_batch_events_device(self, d_text_ptr, d_offsets_ptr, nseg, n, min_len, d_events_ptr, cap, d_nevents_ptr,
+                                 stream_ptr):
+        """pm_hip_scan_batch_events_device: scan_batch_device's streams, but
+        the output is the match list: one u64 event (position << 24 | gid)
+        per position whose answer has at least min_len bytes, appended at the
+        device u64 cursor d_nevents_ptr into d_events_ptr[0, cap)."""
+        rc = self.lib.pm_hip_scan_batch_events_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, min_len,
+                                                      d_events_ptr, cap, d_nevents_ptr, stream_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def scan_flows_events_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr, min_len,
+                                 d_events_ptr, cap, d_nevents_ptr, stream_ptr):
+        """pm_hip_scan_flows_events_device: scan_flows_device's streams and
+        states with the match list of scan_batch_events_device as output."""
+        rc = self.lib.pm_hip_scan_flows_events_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr,
+                                                      d_state_out_ptr, min_len, d_events_ptr, cap, d_nevents_ptr,
+                                                      stream_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def _read_events(self, data, offsets, state, min_len):
+        """The host events forms: (events u64 ascending, state_out or None).
+        A host buffer too short for the call's events means one more call
+        with room for all of them, from the same states."""
+        arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
+                                   else data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or offs.size < 1 or int(offs[-1]) != len(arr):
+            raise ValueError("offsets: nseg + 1 values, the last one len(data)")
+        nseg = offs.size - 1
+        if state is not None and state.shape != (nseg,):
+            raise ValueError("state: nseg values")
+        cap = max(1024, len(arr) // 16)
+        while True:
+            ev = np.empty(cap, dtype=np.uint64)
+            total = ctypes.c_size_t(0)
+            st = None if state is None else state.copy()
+            head = (self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                    offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg)
+            tail = (min_len, ev.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), cap, ctypes.byref(total))
+            if state is None:
+                rc = self.lib.pm_hip_read_batch_events(*head, *tail)
+            else:
+                rc = self.lib.pm_hip_read_flows_events(*head, st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), *tail)
+            if rc != 0:
+                raise RuntimeError(self.lib.pm_hip_last_error().decode())
+            if total.value <= cap:
+                return ev[:total.value], st
+            cap = total.value
+
+    def read_batch_events(self, data, offsets, min_len=3):
+        """pm_hip_read_batch_events: (positions int64, codes) of the positions
+        of read_batch_codes' answer where a pattern of at least min_len bytes
+        ends, in position order; codes as read_batch_codes gives them."""
+        ev, _ = self._read_events(data, offsets, None, min_len)
+        pos, gids = unpack_events(ev)
+        return pos, self._codes[gids]
+
+    def read_many_events(self, buffers, min_len=3):
+        """One batch events call over a list of bytes-like streams: per
+        stream, in order, (positions inside the stream, codes)."""
+        offs = batch_offsets(buffers)
+        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
+        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        pos, codes = self.read_batch_events(data, offs, min_len)
+        return _split_events(pos, codes, offs)
+
+    def read_flows_events(self, data, offsets, state=None, min_len=3):
+        """pm_hip_read_flows_events: (positions, codes, state_out) -- the
+        events of read_flows_codes' answer and the flows' states, which
+        advance exactly as in read_flows_codes."""
+        nseg = len(offsets) - 1
+        st = np.zeros(nseg, dtype=np.uint32) if state is None else np.array(state, dtype=np.uint32, order="C")
+        ev, st = self._read_events(data, offsets, st, min_len)
+        pos, gids = unpack_events(ev)
+        return pos, self._codes[gids], st
 
     # --- flow scan: the batched layout with a carried state per stream -----
     def scan_flows_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr, d_out_ptr,
