@@ -218,7 +218,8 @@ uint32_t pm_hip_flow_states(void* obj);
  * at most one event per position.  Position i emits an event iff its answer
  * g != 0 and pm_hip_pattern_len(g) >= min_len.  The answer is the longest
  * pattern ending at i, so this is "some pattern of at least min_len bytes
- * ends here" and the filter loses nothing; with min_len >= 3 the patterns of
+ * ends here" and the filter loses nothing for that question (WHICH patterns
+ * end there: the all-matches forms below); with min_len >= 3 the patterns of
  * <= 2 bytes, whose gids come first, are rejected by one compare.
  * Text, offsets and states mean exactly what they mean in
  * pm_hip_scan_batch_device / pm_hip_scan_flows_device, with the same memory
@@ -276,6 +277,54 @@ int pm_hip_read_batch_events(void* obj, const uint8_t* buf, const int64_t* offse
                              uint64_t* events, size_t cap, size_t* nevents);
 int pm_hip_read_flows_events(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                              uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents);
+
+/*
+ * All matches: the match list with an event for EVERY pattern that ends at a
+ * position, not only the longest.  The events forms above follow read_char's
+ * contract (one answer per position); their filter loses nothing for "does
+ * some pattern of at least min_len bytes end here", but a caller that keys a
+ * rule on each pattern also needs the shorter ones: with "/admin" and "admin"
+ * in the dictionary, a position where "/admin" ends is also one where "admin"
+ * ends.  Every pattern ending at i is a suffix of the answer g, so it lies on
+ * g's suffix chain g, parent[g], parent[parent[g]], ... (pm_hip_parent_gid;
+ * the patterns tree of PatternsTree.c).  Position i emits one event
+ * i << 24 | h for every h on that chain with pm_hip_pattern_len(h) >= min_len.
+ * Lengths fall strictly along the chain, so these are its first members.
+ * The device forms have the arguments, return codes, alignment rules, memory
+ * safety, serve_stop behaviour, nseg == 0 / n == 0 cases and
+ * pm_hip_kernel_last / pm_hip_dfa_form_last values of
+ * pm_hip_scan_batch_events_device / pm_hip_scan_flows_events_device, allocate
+ * nothing and may be captured.  They differ in the list alone: a position may
+ * bring several events, *d_nevents grows by all of them, and the total may
+ * exceed n (chains of up to pm_flat_array("depth")'s maximum: 17-24 in the
+ * shipped dictionaries).  So size cap from a count-only call (cap == 0,
+ * d_events == NULL) or from a bound such as n times the largest depth, not
+ * from n.  Order in the device list is unspecified.
+ * The host forms behave like pm_hip_read_*_events (same staging, first launch
+ * max(1024, n / 16) slots or "events_cap", one relaunch from the same input
+ * states when the list was short, states written back from the complete
+ * scan); the list is sorted ascending as plain u64: by position, then by gid
+ * within a position (NOT by length: gid order is pm_assign_gids').
+ * Measured (64 MiB, min_len 3, profiles/matches/): on random ASCII, where
+ * chains are rare (the list grows 1.003-1.004x), the calls take 0.79-0.93x
+ * the time of their dense u32 siblings and 0.95-1.03x that of the events
+ * forms.  On the lines stream the list grows 1.5-1.6x (an event per 4 bytes,
+ * 8 B each) and the calls take 1.04-1.05x (batch) and 1.6-1.9x (flows) the
+ * dense call: a caller with match-dense input gains no device time over the
+ * ids, only the host walk over the parents (pm_flat_expand_matches does that
+ * walk on the host for a caller that keeps the ids).
+ */
+int pm_hip_scan_batch_matches_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                     int64_t n, uint32_t min_len, uint64_t* d_events, uint64_t cap,
+                                     unsigned long long* d_nevents, void* hip_stream);
+int pm_hip_scan_flows_matches_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                     int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t min_len,
+                                     uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                     void* hip_stream);
+int pm_hip_read_batch_matches(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t min_len,
+                              uint64_t* events, size_t cap, size_t* nevents);
+int pm_hip_read_flows_matches(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                              uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents);
 
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,
@@ -494,6 +543,14 @@ uint32_t pm_flat_flow_states(void* handle);
 /* n_short: gids 1 .. n_short are exactly the patterns of <= 2 bytes (the
  * events kernels' reject without a load rests on it). */
 uint32_t pm_flat_short_gids(void* handle);
+/* The all-matches list (above) of n dense gids on the host, for either image
+ * kind: the position is the index, the list ascends as plain u64 (position,
+ * then gid), *nevents = the total, and only the first min(cap, total) events
+ * are stored.  A gid out of range counts as no match.  Returns 0; -2 for
+ * min_len == 0, n > 2^40, nevents NULL, or a NULL array with a non-zero
+ * count; -4 with 2^24 or more patterns. */
+int pm_flat_expand_matches(void* handle, const uint32_t* gids, size_t n, uint32_t min_len, uint64_t* events,
+                           size_t cap, size_t* nevents);
 void pm_flat_free(void* handle);
 
 #ifdef __cplusplus

@@ -17,7 +17,10 @@ interface:
                     (HipMatcher.read_flows_* / scan_flows_device)
     unpack_events   (positions, gids) of the match list the events forms of
                     both scans give (HipMatcher.read_*_events /
-                    scan_*_events_device)
+                    scan_*_events_device) and, with every pattern that
+                    ends at a position, their all-matches forms
+                    (HipMatcher.read_*_matches / scan_*_matches_device,
+                    FlowTable.scan_matches)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401

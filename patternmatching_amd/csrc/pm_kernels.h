@@ -152,6 +152,24 @@ hipError_t pm_launch_rt_batch_events(const uint8_t* text, const int64_t* offsets
 hipError_t pm_launch_dfa_flows_events(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
                                       const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
                                       const DfaDev& t, uint32_t states, int64_t force_seg, int num_cu, hipStream_t s);
+// What the all-matches forms add (pm_hip.h, "all matches"): the patterns
+// tree's parent[] in gid space (PmParents; every value below n_patterns + 1)
+// and the largest depth[], which bounds the rounds of a chain's expansion
+// whatever parent[] holds.
+struct MatchDev {
+    const uint32_t* parent;
+    uint32_t max_depth;
+};
+// pm_launch_rt_batch_events / pm_launch_dfa_flows_events with an event for
+// every pattern that ends at a position, not only the longest
+// (rt_batch_matches_kernel, dfa_flow_matches_kernel): arguments, launch shapes
+// and memory safety are theirs; *cursor may end above n.
+hipError_t pm_launch_rt_batch_matches(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                      const EvDev& ev, const MatchDev& mx, const RtDev& t, int num_cu, hipStream_t s);
+hipError_t pm_launch_dfa_flows_matches(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                       const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
+                                       const MatchDev& mx, const DfaDev& t, uint32_t states, int64_t force_seg,
+                                       int num_cu, hipStream_t s);
 // The sparse kernel (PmSparseKernel) a launch of this width runs, 0 when
 // it runs dense rows: the forced DfaDev::sparse_kernel where the object
 // and width allow it, else the product choice.

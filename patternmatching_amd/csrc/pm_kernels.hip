@@ -2113,6 +2113,231 @@ __global__ __launch_bounds__(DFA_THREADS) void dfa_flow_events_kernel(
             if (offs[j + 1] <= offs[j]) state_out[j] = load_state(j);
 }
 
+// ---- all matches: every pattern that ends at a position ----------------------
+// The all-matches forms of the two events kernels (pm_hip.h, "all matches"):
+// position i with answer g emits an event for g and for every pattern on g's
+// suffix chain (parent[g], parent[parent[g]], ...; PmParents) that passes
+// ev_keep.  Lengths fall strictly along a chain, so the kept members are a
+// prefix of it and a lane's chain ends at the first member that fails; gid 0
+// (the chain's end) fails for every min_len.
+// They are kernels of their own, rt_batch_events_kernel's and
+// dfa_flow_events_kernel's text with the expansion added after a step's
+// heads were staged (everything up to there -- walk, seeks, clamps, states,
+// the empty streams' copy pass -- is theirs unchanged, and their comments
+// hold).  Sharing the text through a body template with an ALL argument was
+// built and rejected: inlined into the longest-only kernels it reorders a
+// handful of their instructions (the gfx950 assembly differs in scheduling),
+// and their code has to stay what it was.
+// The expansion runs in rounds: in a round every lane replaces its pending
+// gids by their parents, drops those that fail the filter, and the wave ranks
+// the survivors, reserves once and puts them -- the heads' own ranking
+// (ballot + mbcnt, or wave_scan_incl over the lanes' counts), once per chain
+// level.  Every round is reached from wave-uniform control flow (the loop
+// count and the ballot / __any tests are uniform), as ev_reserve and ev_flush
+// need.  A round of the flow kernel can hold up to 1,024 events and then
+// takes ev_reserve's direct path; one of the batched kernel holds at most 64.
+// The flow kernel walks r[16] in place, so it needs no registers beyond its
+// sibling's.
+// Memory safety does not depend on the data: a gid read from parent[] is
+// below n_patterns + 1 (values_ok, pm_flatten.cpp) like the answers
+// themselves, so parent[] and len[] are read in bounds; the rounds are
+// bounded by max_depth, the largest depth[] of the image, so a damaged
+// table cannot spin a wave; and ev_put stores below cap only.
+template <bool SMALL>
+__global__ __launch_bounds__(RT_THREADS) void rt_batch_matches_kernel(const uint8_t* __restrict__ text,
+                                                                      const int64_t* __restrict__ offs, int64_t nseg,
+                                                                      int64_t n, EvDev ev, MatchDev mx, RtDev t) {
+    constexpr int kT12Words = SMALL ? 0 : RT_T2_U16 / 2;
+    constexpr int kStageWords = (RT_THREADS / 64) * RT_EV_STAGE * 2;
+    __shared__ __attribute__((aligned(16))) uint32_t s_lds[kT12Words + kStageWords + RT_BATCH_TILE / 32];
+    uint32_t* const s_mask = s_lds + kT12Words + kStageWords;
+    const uint16_t* s_t = t.t12;
+    const int tid = threadIdx.x;
+    EvWave<RT_EV_STAGE> stage{reinterpret_cast<uint64_t*>(s_lds + kT12Words) + (tid >> 6) * RT_EV_STAGE, 0u};
+    if (!SMALL) {
+        const uint4* src = reinterpret_cast<const uint4*>(t.t12);
+        uint4* dst = reinterpret_cast<uint4*>(s_lds);
+        for (int k = tid; k < RT_T2_U16 * 2 / 16; k += RT_THREADS) dst[k] = src[k];
+        __syncthreads();
+        s_t = reinterpret_cast<const uint16_t*>(s_lds);
+    }
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t T0 = ntiles * (int64_t)blockIdx.x / (int64_t)gridDim.x;
+    const int64_t T1 = ntiles * ((int64_t)blockIdx.x + 1) / (int64_t)gridDim.x;
+    const int64_t noffs = nseg + 1;
+    int64_t a = batch_seek(offs, 0, noffs, T0 * RT_BATCH_TILE + 1);
+    for (int64_t T = T0; T < T1; ++T) {
+        const int64_t base = T * RT_BATCH_TILE;
+        const int64_t end = base + RT_BATCH_TILE < n ? base + RT_BATCH_TILE : n;
+        a = batch_seek(offs, a, noffs, base + 1);
+        const int64_t b = batch_seek(offs, a, noffs, end);
+        int64_t start = a > 0 ? (int64_t)rfl64((uint64_t)offs[a - 1]) : 0;
+        if (b > a) {  // workgroup-uniform
+            __syncthreads();
+            if (tid < RT_BATCH_TILE / 32) s_mask[tid] = 0u;
+            __syncthreads();
+            for (int64_t j = a + tid; j < b; j += RT_THREADS) {
+                const int64_t rel = offs[j] - base;
+                if (rel > 0 && rel < RT_BATCH_TILE) atomicOr(&s_mask[rel >> 5], 1u << (rel & 31));
+            }
+            __syncthreads();
+            int w = tid >> 5;
+            uint32_t m = s_mask[w] & (0xFFFFFFFFu >> (31 - (tid & 31)));
+            while (!m && w > 0) m = s_mask[--w];
+            if (m) start = base + w * 32 + 31 - __clz(m);
+        }
+        const int64_t i = base + tid;
+        uint32_t v = 0;
+        if (i < n) {
+            start = start < 0 ? 0 : start > i ? i : start;
+            v = rt_one(text, s_t, t, i, start);
+        }
+        // all 64 lanes of every wave are here (a lane past n holds v = 0)
+        const bool keep = ev_keep(v, ev);
+        const uint64_t km = __ballot(keep);
+        if (km) {
+            const EvSlot slot = ev_reserve(stage, (uint32_t)__popcll(km), ev);
+            if (keep) ev_put(stage, slot, wave_prefix(km), (uint64_t)i << PM_EV_GID_BITS | v, ev);
+            uint32_t h = keep ? v : 0u;  // the lane's pending chain member, 0 = done
+            for (uint32_t d = 1; d < mx.max_depth; ++d) {  // wave-uniform
+                if (h) {
+                    h = mx.parent[h];
+                    if (!ev_keep(h, ev)) h = 0u;
+                }
+                const uint64_t hm = __ballot(h != 0u);
+                if (!hm) break;
+                const EvSlot hs = ev_reserve(stage, (uint32_t)__popcll(hm), ev);
+                if (h) ev_put(stage, hs, wave_prefix(hm), (uint64_t)i << PM_EV_GID_BITS | h, ev);
+            }
+        }
+        a = b;
+    }
+    ev_flush(stage, ev);
+}
+
+template <bool CODED>
+__global__ __launch_bounds__(DFA_THREADS) void dfa_flow_matches_kernel(
+    const uint8_t* __restrict__ text, const int64_t* __restrict__ offs, int64_t nseg, int64_t n,
+    const uint32_t* __restrict__ state_in, uint32_t* __restrict__ state_out, EvDev ev, MatchDev mx,
+    const uint32_t* __restrict__ nxt, const uint32_t* __restrict__ outt, uint32_t states, int64_t warm,
+    int64_t seg_len, const uint32_t* __restrict__ gram3) {
+    __shared__ uint64_t s_stage[(DFA_THREADS / 64) * DFA_EV_STAGE];
+    EvWave<DFA_EV_STAGE> stage{s_stage + (threadIdx.x >> 6) * DFA_EV_STAGE, 0u};
+    const int64_t nlane = (n + seg_len - 1) / seg_len;
+    const int64_t stride = (int64_t)gridDim.x * DFA_THREADS;
+    const int64_t gtid = (int64_t)blockIdx.x * DFA_THREADS + threadIdx.x;
+    const int64_t noffs = nseg + 1;
+    auto load_state = [&](int64_t j) -> uint32_t {  // j in [0, nseg)
+        const uint32_t s = state_in ? state_in[j] : 0u;
+        return s < states ? s : 0u;
+    };
+    for (int64_t sg0 = gtid - (threadIdx.x & 63); sg0 < nlane; sg0 += stride) {  // wave-uniform
+        const int64_t sg = sg0 + (threadIdx.x & 63);
+        int64_t i = 0, hi = 0, end = 0, j = 0;  // a lane without a segment: no step
+        uint32_t s = 0;
+        if (sg < nlane) {
+            const int64_t lo = sg * seg_len;
+            hi = lo + seg_len < n ? lo + seg_len : n;
+            // the stream holding lo: the first offset > lo, minus one
+            j = flow_seek(offs, 0, noffs, lo + 1) - 1;
+            j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+            int64_t start = offs[j];
+            start = start < 0 ? 0 : start > lo ? lo : start;
+            end = offs[j + 1];
+            int64_t wlo = lo - warm;
+            if (wlo < start) wlo = start;
+            int64_t w = wlo;
+            if (gram3) w = dfa_sync_lo(text, lo, wlo, gram3);  // in [wlo, lo]: never before start
+            s = (w == wlo && wlo == start) ? load_state(j) : 0u;
+            for (int64_t k = w; k < lo; ++k) {
+                const uint32_t v = nxt[(size_t)s * 256 + text[k]];
+                s = CODED ? v & DFA_STATE_MASK : v;
+            }
+            i = lo;
+        }
+        while (__any(i < hi)) {  // wave-uniform: one step of every lane that has positions left
+            const int64_t p0 = i;
+            uint32_t r[16];
+            uint32_t keep = 0;  // bit q: position p0 + q is an event, its gid r[q]
+            if (i < hi) {
+                if ((i & 15) == 0 && i + 16 <= hi && i + 16 <= end) {
+                    const uint4 tw = *reinterpret_cast<const uint4*>(text + i);
+                    const uint32_t W[4] = {tw.x, tw.y, tw.z, tw.w};
+                    uint32_t st[16];
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const uint32_t v = nxt[(size_t)s * 256 + ((W[q >> 2] >> (8 * (q & 3))) & 0xFFu)];
+                        s = CODED ? v & DFA_STATE_MASK : v;
+                        r[q] = CODED ? v >> 20 : 0u;
+                        st[q] = s;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        if (CODED) r[q] = r[q] == DFA_ESC ? outt[st[q]] : r[q];
+                        else r[q] = outt[st[q]];
+                        keep |= (uint32_t)ev_keep(r[q], ev) << q;
+                    }
+                    i += 16;
+                } else {
+                    const uint32_t v = nxt[(size_t)s * 256 + text[i]];
+                    s = CODED ? v & DFA_STATE_MASK : v;
+                    uint32_t id = CODED ? v >> 20 : outt[s];
+                    if (CODED && id == DFA_ESC) id = outt[s];
+                    r[0] = id;
+                    keep = (uint32_t)ev_keep(id, ev);
+                    ++i;
+                }
+                if (i == end) {  // position end - 1 was stream j's last byte
+                    if (state_out) state_out[j] = s;
+                    if (i < hi) {
+                        // the next stream that is not empty: the first offset > i, minus one
+                        j = flow_seek(offs, j + 2 < noffs ? j + 2 : noffs, noffs, i + 1) - 1;
+                        j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+                        end = offs[j + 1];
+                        s = load_state(j);
+                    }
+                }
+            }
+            // all 64 lanes are here
+            if (__any(keep != 0u)) {
+                const uint32_t c = __popc(keep);
+                const uint32_t incl = wave_scan_incl(c);
+                const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
+                const EvSlot slot = ev_reserve(stage, total, ev);
+                uint32_t k = incl - c;
+#pragma unroll
+                for (int q = 0; q < 16; ++q)
+                    if ((keep >> q) & 1u)
+                        ev_put(stage, slot, k++, (uint64_t)(p0 + q) << PM_EV_GID_BITS | r[q], ev);
+                for (uint32_t d = 1; d < mx.max_depth; ++d) {  // wave-uniform
+                    // r[q] = parent[r[q]] in place; a member that fails the filter ends its chain
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if ((keep >> q) & 1u) {
+                            const uint32_t h = mx.parent[r[q]];
+                            if (ev_keep(h, ev)) r[q] = h;
+                            else keep &= ~(1u << q);
+                        }
+                    if (!__any(keep != 0u)) break;
+                    const uint32_t hc = __popc(keep);
+                    const uint32_t hincl = wave_scan_incl(hc);
+                    const uint32_t htotal = __builtin_amdgcn_readlane(hincl, 63);
+                    const EvSlot hs = ev_reserve(stage, htotal, ev);
+                    uint32_t hk = hincl - hc;
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if ((keep >> q) & 1u)
+                            ev_put(stage, hs, hk++, (uint64_t)(p0 + q) << PM_EV_GID_BITS | r[q], ev);
+                }
+            }
+        }
+    }
+    ev_flush(stage, ev);
+    if (state_out)  // empty streams keep their state (as used: an invalid one is the root)
+        for (int64_t j = gtid; j < nseg; j += stride)
+            if (offs[j + 1] <= offs[j]) state_out[j] = load_state(j);
+}
+
 // The sparse (default-transition) form, pm_flatten.h: rows only for the
 // states whose row differs from their fallback's in more than PM_SDFA_K
 // bytes, 16-B records for the rest (8-B units in pm_pack_sparse8's
@@ -3370,6 +3595,21 @@ hipError_t pm_launch_rt_batch_events(const uint8_t* text, const int64_t* offsets
     return hipGetLastError();
 }
 
+// Its all-matches form (rt_batch_matches_kernel): the same launch.
+hipError_t pm_launch_rt_batch_matches(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                      const EvDev& ev, const MatchDev& mx, const RtDev& t, int num_cu, hipStream_t s) {
+    if (n <= 0 || nseg <= 0) return hipSuccess;
+    if (!text || !offsets || num_cu <= 0) return hipErrorInvalidValue;
+    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent) return hipErrorInvalidValue;
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
+    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
+    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    if (small) hipLaunchKernelGGL(rt_batch_matches_kernel<true>, g, b, 0, s, text, offsets, nseg, n, ev, mx, t);
+    else hipLaunchKernelGGL(rt_batch_matches_kernel<false>, g, b, 0, s, text, offsets, nseg, n, ev, mx, t);
+    return hipGetLastError();
+}
+
 hipError_t pm_launch_rt_serve(PmServeReq* req, uint64_t* fwd, uint32_t* done, int blocks, uint64_t seen,
                               uint64_t gen, int64_t idle_ticks, const RtDev& t, hipStream_t s) {
     if (blocks <= 0) return hipErrorInvalidValue;
@@ -3620,6 +3860,28 @@ hipError_t pm_launch_dfa_flows_events(const uint8_t* text, const int64_t* offset
     else
         hipLaunchKernelGGL(dfa_flow_events_kernel<false>, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev,
                            t.next, t.out, states, t.warm, seg, g3);
+    return hipGetLastError();
+}
+
+// Its all-matches form (dfa_flow_matches_kernel): the same launch.
+hipError_t pm_launch_dfa_flows_matches(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                       const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
+                                       const MatchDev& mx, const DfaDev& t, uint32_t states, int64_t force_seg,
+                                       int num_cu, hipStream_t s) {
+    if (nseg <= 0 || n < 0 || (n == 0 && !state_out)) return hipSuccess;
+    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
+    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent) return hipErrorInvalidValue;
+    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
+    int64_t seg, blocks;
+    if (!flow_shape(nseg, n, 16, force_seg, num_cu, seg, blocks)) return hipErrorInvalidValue;
+    const dim3 g((unsigned)blocks), b(DFA_THREADS);
+    const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
+    if (t.coded)
+        hipLaunchKernelGGL(dfa_flow_matches_kernel<true>, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev,
+                           mx, t.next, t.out, states, t.warm, seg, g3);
+    else
+        hipLaunchKernelGGL(dfa_flow_matches_kernel<false>, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev,
+                           mx, t.next, t.out, states, t.warm, seg, g3);
     return hipGetLastError();
 }
 

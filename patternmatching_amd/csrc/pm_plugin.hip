@@ -276,6 +276,7 @@ struct PmHip {
     const uint32_t* d_parent = nullptr;  // PmParents, gid space (scoring)
     const uint32_t* d_depth = nullptr;
     const uint32_t* d_len = nullptr;  // PmGidMap::len (the events kernels' filter)
+    uint32_t max_depth = 0;           // the largest depth[]: bounds the all-matches kernels' chain walk
     std::vector<uint32_t> parent;
     std::string cache_dir;   // compiled-image cache (else $PM_IMAGE_CACHE)
     bool cache_hit = false;
@@ -1305,6 +1306,7 @@ void pm_hip_compile(void* obj) {
     init_pick(o->pick, o->kind, o->dfa.sbase != nullptr);
     o->d_parent = (const uint32_t*)dalloc_copy(o, im.par.parent.data(), im.par.parent.size() * 4);
     o->d_depth = (const uint32_t*)dalloc_copy(o, im.par.depth.data(), im.par.depth.size() * 4);
+    o->max_depth = im.par.depth.empty() ? 0u : *std::max_element(im.par.depth.begin(), im.par.depth.end());
     o->parent = std::move(im.par.parent);
     o->d_len = (const uint32_t*)dalloc_copy(o, o->gids.len.data(), o->gids.len.size() * 4);
     o->id_of_gid.assign(o->gids.index_of_gid.size(), PM_NULL_PATTERN_ID);
@@ -1784,10 +1786,13 @@ static EvDev events_dev(PmHip* o, uint32_t min_len, uint64_t* d_events, uint64_t
     return EvDev{d_events, cap, d_nevents, o->d_len, o->gids.n_short, min_len};
 }
 
-int pm_hip_scan_batch_events_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
-                                    int64_t n, uint32_t min_len, uint64_t* d_events, uint64_t cap,
-                                    unsigned long long* d_nevents, void* hip_stream) {
-    PmHip* o = as(obj);
+static MatchDev matches_dev(PmHip* o) { return MatchDev{o->d_parent, o->max_depth}; }
+
+// The batched events call; all: an event for every pattern ending at a
+// position (pm_hip_scan_batch_matches_device), not only the longest.
+static int scan_batch_events(PmHip* o, bool all, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                             int64_t n, uint32_t min_len, uint64_t* d_events, uint64_t cap,
+                             unsigned long long* d_nevents, void* hip_stream) {
     if (const int rc = batch_check(o)) return rc;
     if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) ||
         (nseg > 0 && n > 0 && (!d_text || !d_offsets))) {
@@ -1799,11 +1804,14 @@ int pm_hip_scan_batch_events_device(void* obj, const uint8_t* d_text, const int6
     if (nseg == 0 || n == 0) return 0;
     hipError_t e = hipSetDevice(o->device);
     serve_stop(o);  // a device launch wants the whole device
-    if (e == hipSuccess)
-        e = pm_launch_rt_batch_events(d_text, d_offsets, nseg, n, events_dev(o, min_len, d_events, cap, d_nevents),
-                                      o->rt, o->num_cu, (hipStream_t)hip_stream);
+    if (e == hipSuccess) {
+        const EvDev ev = events_dev(o, min_len, d_events, cap, d_nevents);
+        e = all ? pm_launch_rt_batch_matches(d_text, d_offsets, nseg, n, ev, matches_dev(o), o->rt, o->num_cu,
+                                             (hipStream_t)hip_stream)
+                : pm_launch_rt_batch_events(d_text, d_offsets, nseg, n, ev, o->rt, o->num_cu, (hipStream_t)hip_stream);
+    }
     if (e != hipSuccess) {
-        std::snprintf(g_err, sizeof(g_err), "batch events launch: %s", hipGetErrorString(e));
+        std::snprintf(g_err, sizeof(g_err), "batch %s launch: %s", all ? "matches" : "events", hipGetErrorString(e));
         return -3;
     }
     o->last_kernel = KIND_RT;
@@ -1811,11 +1819,24 @@ int pm_hip_scan_batch_events_device(void* obj, const uint8_t* d_text, const int6
     return 0;
 }
 
-int pm_hip_scan_flows_events_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
-                                    int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t min_len,
-                                    uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
-                                    void* hip_stream) {
-    PmHip* o = as(obj);
+int pm_hip_scan_batch_events_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, uint32_t min_len, uint64_t* d_events, uint64_t cap,
+                                    unsigned long long* d_nevents, void* hip_stream) {
+    return scan_batch_events(as(obj), false, d_text, d_offsets, nseg, n, min_len, d_events, cap, d_nevents,
+                             hip_stream);
+}
+
+int pm_hip_scan_batch_matches_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                     int64_t n, uint32_t min_len, uint64_t* d_events, uint64_t cap,
+                                     unsigned long long* d_nevents, void* hip_stream) {
+    return scan_batch_events(as(obj), true, d_text, d_offsets, nseg, n, min_len, d_events, cap, d_nevents,
+                             hip_stream);
+}
+
+// The flow events call; all as in scan_batch_events.
+static int scan_flows_events(PmHip* o, bool all, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                             int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t min_len,
+                             uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents, void* hip_stream) {
     if (const int rc = flows_check(o)) return rc;
     if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_state_in & 3) ||
         ((uintptr_t)d_state_out & 3) || (d_state_in && d_state_in == d_state_out) ||
@@ -1830,17 +1851,36 @@ int pm_hip_scan_flows_events_device(void* obj, const uint8_t* d_text, const int6
     if (nseg == 0 || (n == 0 && !d_state_out)) return 0;
     hipError_t e = hipSetDevice(o->device);
     serve_stop(o);  // a device launch wants the whole device
-    if (e == hipSuccess)
-        e = pm_launch_dfa_flows_events(d_text, d_offsets, nseg, n, d_state_in, d_state_out,
-                                       events_dev(o, min_len, d_events, cap, d_nevents), o->dfa, o->dfa_states,
-                                       o->flow_seg, o->num_cu, (hipStream_t)hip_stream);
+    if (e == hipSuccess) {
+        const EvDev ev = events_dev(o, min_len, d_events, cap, d_nevents);
+        e = all ? pm_launch_dfa_flows_matches(d_text, d_offsets, nseg, n, d_state_in, d_state_out, ev, matches_dev(o),
+                                              o->dfa, o->dfa_states, o->flow_seg, o->num_cu, (hipStream_t)hip_stream)
+                : pm_launch_dfa_flows_events(d_text, d_offsets, nseg, n, d_state_in, d_state_out, ev, o->dfa,
+                                             o->dfa_states, o->flow_seg, o->num_cu, (hipStream_t)hip_stream);
+    }
     if (e != hipSuccess) {
-        std::snprintf(g_err, sizeof(g_err), "flow events launch: %s", hipGetErrorString(e));
+        std::snprintf(g_err, sizeof(g_err), "flow %s launch: %s", all ? "matches" : "events", hipGetErrorString(e));
         return -3;
     }
     o->last_kernel = KIND_AC;
     o->last_form = 1;
     return 0;
+}
+
+int pm_hip_scan_flows_events_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t min_len,
+                                    uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                    void* hip_stream) {
+    return scan_flows_events(as(obj), false, d_text, d_offsets, nseg, n, d_state_in, d_state_out, min_len, d_events,
+                             cap, d_nevents, hip_stream);
+}
+
+int pm_hip_scan_flows_matches_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                     int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t min_len,
+                                     uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                     void* hip_stream) {
+    return scan_flows_events(as(obj), true, d_text, d_offsets, nseg, n, d_state_in, d_state_out, min_len, d_events,
+                             cap, d_nevents, hip_stream);
 }
 
 uint32_t pm_hip_pattern_len(void* obj, uint32_t gid) {
@@ -1855,7 +1895,7 @@ uint32_t pm_hip_pattern_len(void* obj, uint32_t gid) {
 // the first launch changed nothing the second reads).  Then only the events
 // come back, are sorted, and the first min(cap, total) handed over.
 // Everything is checked before anything is written.
-static int read_events(PmHip* o, bool flows, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                        uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents) {
     if (const int rc = flows ? flows_check(o) : batch_check(o)) return rc;
     bool ok = (nseg == 0 || offsets) && nseg < ((size_t)1 << 60);
@@ -1910,14 +1950,23 @@ static int read_events(PmHip* o, bool flows, const uint8_t* buf, const int64_t* 
         }
         PM_CHECK(hipMemsetAsync(q.d_nev, 0, sizeof(unsigned long long), q.s));
         const EvDev ev = events_dev(o, min_len, q.d_ev, dcap, q.d_nev);
-        const hipError_t e =
-            flows ? pm_launch_dfa_flows_events(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, st ? q.d_st_in : nullptr,
-                                               st ? q.d_st_out : nullptr, ev, o->dfa, o->dfa_states, o->flow_seg,
-                                               o->num_cu, q.s)
-                  : pm_launch_rt_batch_events(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, o->rt, o->num_cu, q.s);
+        const uint32_t* const si = st ? q.d_st_in : nullptr;
+        uint32_t* const so = st ? q.d_st_out : nullptr;
+        hipError_t e;
+        if (all)
+            e = flows ? pm_launch_dfa_flows_matches(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev,
+                                                    matches_dev(o), o->dfa, o->dfa_states, o->flow_seg, o->num_cu, q.s)
+                      : pm_launch_rt_batch_matches(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, matches_dev(o),
+                                                   o->rt, o->num_cu, q.s);
+        else
+            e = flows ? pm_launch_dfa_flows_events(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev, o->dfa,
+                                                   o->dfa_states, o->flow_seg, o->num_cu, q.s)
+                      : pm_launch_rt_batch_events(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, o->rt, o->num_cu,
+                                                  q.s);
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(q.s);
-            std::snprintf(g_err, sizeof(g_err), "%s events launch: %s", flows ? "flow" : "batch", hipGetErrorString(e));
+            std::snprintf(g_err, sizeof(g_err), "%s %s launch: %s", flows ? "flow" : "batch",
+                          all ? "matches" : "events", hipGetErrorString(e));
             return -3;
         }
         PM_CHECK(hipMemcpyAsync(&total, q.d_nev, sizeof(total), hipMemcpyDeviceToHost, q.s));
@@ -1931,7 +1980,8 @@ static int read_events(PmHip* o, bool flows, const uint8_t* buf, const int64_t* 
     if (total) PM_CHECK(hipMemcpyAsync(ev.data(), q.d_ev, ev.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
     if (st) PM_CHECK(hipMemcpyAsync(state, q.d_st_out, nseg * sizeof(uint32_t), hipMemcpyDeviceToHost, q.s));
     PM_CHECK(hipStreamSynchronize(q.s));
-    std::sort(ev.begin(), ev.end());  // position order: the position is the high bits, one event per position
+    // position order: the position is the high bits; all: then the gid within a position
+    std::sort(ev.begin(), ev.end());
     if (cap && total) std::memcpy(events, ev.data(), std::min<size_t>(cap, ev.size()) * sizeof(uint64_t));
     *nevents = (size_t)total;
     return 0;
@@ -1939,12 +1989,22 @@ static int read_events(PmHip* o, bool flows, const uint8_t* buf, const int64_t* 
 
 int pm_hip_read_batch_events(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t min_len,
                              uint64_t* events, size_t cap, size_t* nevents) {
-    return read_events(as(obj), false, buf, offsets, nseg, nullptr, min_len, events, cap, nevents);
+    return read_events(as(obj), false, false, buf, offsets, nseg, nullptr, min_len, events, cap, nevents);
+}
+
+int pm_hip_read_batch_matches(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t min_len,
+                              uint64_t* events, size_t cap, size_t* nevents) {
+    return read_events(as(obj), false, true, buf, offsets, nseg, nullptr, min_len, events, cap, nevents);
 }
 
 int pm_hip_read_flows_events(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                              uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents) {
-    return read_events(as(obj), true, buf, offsets, nseg, state, min_len, events, cap, nevents);
+    return read_events(as(obj), true, false, buf, offsets, nseg, state, min_len, events, cap, nevents);
+}
+
+int pm_hip_read_flows_matches(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                              uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents) {
+    return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents);
 }
 
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,
@@ -2379,6 +2439,37 @@ uint32_t pm_flat_flow_states(void* handle) {
 }
 
 uint32_t pm_flat_short_gids(void* handle) { return static_cast<PmFlatHandle*>(handle)->g.n_short; }
+
+// The all-matches list of dense gids on the host: position k's chain
+// (gids[k], parent[gids[k]], ...) while the member's length is at least
+// min_len -- lengths fall strictly along a chain, so the walk stops at the
+// first shorter one.  A chain's gids are unordered, so each position's events
+// are sorted before they are handed over; positions ascend by themselves.
+// A gid out of range counts as no match, and depth[] bounds the walk.
+int pm_flat_expand_matches(void* handle, const uint32_t* gids, size_t n, uint32_t min_len, uint64_t* events,
+                           size_t cap, size_t* nevents) {
+    PmFlatHandle* h = static_cast<PmFlatHandle*>(handle);
+    if (min_len == 0 || n > ((size_t)1 << 40) || !nevents || (n && !gids) || (cap && !events)) return -2;
+    const std::vector<uint32_t>& par = h->par.parent;
+    const std::vector<uint32_t>& len = h->g.len;
+    if (par.size() > ((size_t)1 << 24)) return -4;  // a gid has an event's low 24 bits
+    size_t total = 0;
+    std::vector<uint64_t> one;
+    for (size_t k = 0; k < n; ++k) {
+        uint32_t g = gids[k];
+        if (g == 0 || g >= par.size()) continue;
+        one.clear();
+        for (uint32_t d = h->par.depth[g]; d > 0 && g != 0 && len[g] >= min_len; --d, g = par[g])
+            one.push_back((uint64_t)k << 24 | g);
+        std::sort(one.begin(), one.end());
+        for (const uint64_t e : one) {
+            if (total < cap) events[total] = e;
+            ++total;
+        }
+    }
+    *nevents = total;
+    return 0;
+}
 
 void pm_flat_free(void* handle) { delete static_cast<PmFlatHandle*>(handle); }
 

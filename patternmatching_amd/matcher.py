@@ -181,11 +181,21 @@ class FlowTable:
         order, (positions inside the packet, codes) of the positions where a
         pattern of at least min_len bytes ends (HipMatcher.read_flows_events).
         The flows' states advance exactly as in scan()."""
+        return self._scan_list(packets, min_len, self.matcher.read_flows_events, "scan_events")
+
+    def scan_matches(self, packets, min_len=3):
+        """scan_events() with every pattern that ends at a position, not only
+        the longest (HipMatcher.read_flows_matches): per packet (positions,
+        codes), a position once per pattern of at least min_len bytes ending
+        there.  The flows' states advance exactly as in scan()."""
+        return self._scan_list(packets, min_len, self.matcher.read_flows_matches, "scan_matches")
+
+    def _scan_list(self, packets, min_len, read, name):
         keys = [k for k, _ in packets]
         if len(set(keys)) != len(keys):
             seen = set()
             dup = next(k for k in keys if k in seen or seen.add(k))
-            raise ValueError(f"flow {dup!r} appears twice in one scan_events(): concatenate its packets")
+            raise ValueError(f"flow {dup!r} appears twice in one {name}(): concatenate its packets")
         if not packets:
             return []
         bufs = [b for _, b in packets]
@@ -194,7 +204,7 @@ class FlowTable:
                  else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in bufs]
         data = np.concatenate(parts)
         state = np.array([self.states.get(k, 0) for k in keys], dtype=np.uint32)
-        pos, codes, state = self.matcher.read_flows_events(data, offs, state, min_len)
+        pos, codes, state = read(data, offs, state, min_len)
         for k, s in zip(keys, state.tolist()):
             self.states[k] = s
         return _split_events(pos, codes, offs)
@@ -409,10 +419,11 @@ class HipMatcher:
         if rc != 0:
             raise RuntimeError(self.lib.pm_hip_last_error().decode())
 
-    def _read_events(self, data, offsets, state, min_len):
-        """The host events forms: (events u64 ascending, state_out or None).
-        A host buffer too short for the call's events means one more call
-        with room for all of them, from the same states."""
+    def _read_events(self, data, offsets, state, min_len, all_matches=False):
+        """The host events forms (all_matches: the *_matches ones): (events
+        u64 ascending, state_out or None).  A host buffer too short for the
+        call's events means one more call with room for all of them, from
+        the same states."""
         arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
                                    else data, dtype=np.uint8)
         offs = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -430,9 +441,11 @@ class HipMatcher:
                     offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg)
             tail = (min_len, ev.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), cap, ctypes.byref(total))
             if state is None:
-                rc = self.lib.pm_hip_read_batch_events(*head, *tail)
+                fn = self.lib.pm_hip_read_batch_matches if all_matches else self.lib.pm_hip_read_batch_events
+                rc = fn(*head, *tail)
             else:
-                rc = self.lib.pm_hip_read_flows_events(*head, st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), *tail)
+                fn = self.lib.pm_hip_read_flows_matches if all_matches else self.lib.pm_hip_read_flows_events
+                rc = fn(*head, st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), *tail)
             if rc != 0:
                 raise RuntimeError(self.lib.pm_hip_last_error().decode())
             if total.value <= cap:
@@ -464,6 +477,54 @@ class HipMatcher:
         nseg = len(offsets) - 1
         st = np.zeros(nseg, dtype=np.uint32) if state is None else np.array(state, dtype=np.uint32, order="C")
         ev, st = self._read_events(data, offsets, st, min_len)
+        pos, gids = unpack_events(ev)
+        return pos, self._codes[gids], st
+
+    # --- all matches: every pattern that ends at a position ----------------
+    def scan_batch_matches_device(self, d_text_ptr, d_offsets_ptr, nseg, n, min_len, d_events_ptr, cap, d_nevents_ptr,
+                                  stream_ptr):
+        """pm_hip_scan_batch_matches_device: scan_batch_events_device with an
+        event for every pattern of at least min_len bytes that ends at a
+        position (the answer's suffix chain), not only the longest; the
+        cursor may end above n."""
+        rc = self.lib.pm_hip_scan_batch_matches_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, min_len,
+                                                       d_events_ptr, cap, d_nevents_ptr, stream_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def scan_flows_matches_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr, min_len,
+                                  d_events_ptr, cap, d_nevents_ptr, stream_ptr):
+        """pm_hip_scan_flows_matches_device: scan_flows_events_device with the
+        list of scan_batch_matches_device."""
+        rc = self.lib.pm_hip_scan_flows_matches_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr,
+                                                       d_state_out_ptr, min_len, d_events_ptr, cap, d_nevents_ptr,
+                                                       stream_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def read_batch_matches(self, data, offsets, min_len=3):
+        """pm_hip_read_batch_matches: read_batch_events with every pattern
+        that ends at a position: (positions int64, codes), ascending by
+        position and, within a position, by gid."""
+        ev, _ = self._read_events(data, offsets, None, min_len, all_matches=True)
+        pos, gids = unpack_events(ev)
+        return pos, self._codes[gids]
+
+    def read_many_matches(self, buffers, min_len=3):
+        """read_many_events with every pattern that ends at a position."""
+        offs = batch_offsets(buffers)
+        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
+        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        pos, codes = self.read_batch_matches(data, offs, min_len)
+        return _split_events(pos, codes, offs)
+
+    def read_flows_matches(self, data, offsets, state=None, min_len=3):
+        """pm_hip_read_flows_matches: read_flows_events with every pattern
+        that ends at a position: (positions, codes, state_out)."""
+        nseg = len(offsets) - 1
+        st = np.zeros(nseg, dtype=np.uint32) if state is None else np.array(state, dtype=np.uint32, order="C")
+        ev, st = self._read_events(data, offsets, st, min_len, all_matches=True)
         pos, gids = unpack_events(ev)
         return pos, self._codes[gids], st
 
