@@ -326,6 +326,76 @@ int pm_hip_read_batch_matches(void* obj, const uint8_t* buf, const int64_t* offs
 int pm_hip_read_flows_matches(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                               uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents);
 
+/*
+ * Pattern groups: one merged automaton, a group mask per pattern and one per
+ * stream.  A rule engine gives each packet a subset of the patterns by
+ * protocol, direction and port (Snort's port groups, Suricata's
+ * signature-group heads); here every pattern has a uint32_t mask, bit k =
+ * "member of group k", every stream of a batched or flow call brings the mask
+ * of the groups it is scanned for, and pattern h is VISIBLE to stream j iff
+ * groups[h] & stream_groups[j] != 0.  The filter runs in the kernel, beside
+ * the min_len filter.
+ *   all != 0: position i of stream j emits one event i << 24 | h for every
+ *     pattern h that ends at i, is visible to j and has at least min_len
+ *     bytes: the all-matches list with the invisible patterns removed.
+ *   all == 0: at most one event per position, the longest visible pattern of
+ *     at least min_len bytes that ends at i -- what a matcher compiled from
+ *     the visible patterns alone answers at i (then the min_len test).  This is
+ *     NOT the events list filtered by the mask: where the whole dictionary's
+ *     answer is invisible, a shorter visible pattern on its suffix chain
+ *     (pm_hip_parent_gid) is reported.
+ * pm_hip_set_groups(obj, groups, n): groups[k] is the mask of the k-th
+ * add_pattern call, n the number of patterns added.  Call it after compile()
+ * (-1 before; -2 for a wrong n or NULL groups).  A byte string added twice has
+ * the mask of the add that wins (the later one).  The first call allocates two
+ * u32 tables of n + 1 entries on the device, which count in
+ * pm_hip_table_bytes from then on; a later call overwrites them in place
+ * after a device synchronize -- a rule reload: the caller must have no group
+ * scan in flight.  compile() allocates nothing for groups, the compiled-image
+ * cache does not see them, and an object that never calls it behaves exactly
+ * as before.  pm_hip_pattern_groups(obj, gid): the pattern's mask, 0 out of
+ * range or before pm_hip_set_groups.
+ * The scan calls are pm_hip_scan_batch_matches_device /
+ * pm_hip_scan_flows_matches_device with two more arguments: d_stream_groups,
+ * a DEVICE pointer to nseg masks, 4-byte aligned, NULL = every stream
+ * 0xFFFFFFFF; and all.  The stream index a mask is read at is clamped into
+ * [0, nseg), so no mask is read out of bounds whatever the offsets hold.
+ * Flow states do not depend on the masks: two calls that differ only in them
+ * leave identical d_state_out.  Return codes, alignment rules, memory
+ * safety, serve_stop behaviour, the cursor and cap rules, the nseg == 0 /
+ * n == 0 cases and pm_hip_kernel_last / pm_hip_dfa_form_last are the
+ * siblings'; in addition -7: pm_hip_set_groups was not called (nothing is
+ * launched or written, pm_hip_last_error says so).  The calls allocate
+ * nothing and may be captured.  Order in the device list is unspecified.
+ * The host forms behave like pm_hip_read_*_matches (same staging plus nseg
+ * masks, "events_cap", one relaunch when the list was short, the list sorted
+ * ascending as plain u64, states written back from the complete scan, -2 with
+ * nothing written for bad arguments); stream_groups is a HOST pointer here,
+ * NULL = every stream 0xFFFFFFFF.
+ * Measured (64 MiB, min_len 3, all form, profiles/groups/): on random ASCII
+ * with every stream on all groups the calls take 1.03-1.06x the time of
+ * their all-matches siblings (the batched call on 1,500-byte streams
+ * 1.055-1.060x, the rest 1.03-1.04x); with each stream on one of 8 disjoint
+ * groups 0.98-1.04x.  On the lines stream 1.25-1.49x: every position then
+ * loads its stream's mask and two table entries per chain member.
+ */
+int pm_hip_set_groups(void* obj, const uint32_t* groups, size_t n);
+uint32_t pm_hip_pattern_groups(void* obj, uint32_t gid);
+int pm_hip_scan_batch_groups_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_stream_groups, uint32_t min_len, int all,
+                                    uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                    void* hip_stream);
+int pm_hip_scan_flows_groups_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out,
+                                    const uint32_t* d_stream_groups, uint32_t min_len, int all, uint64_t* d_events,
+                                    uint64_t cap, unsigned long long* d_nevents, void* hip_stream);
+int pm_hip_read_batch_groups(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg,
+                             const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
+                             size_t* nevents);
+int pm_hip_read_flows_groups(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                             const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
+                             size_t* nevents);
+
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,
  * PatternsTree.c:485-494): per position, equal -> success; d_algo's pattern
@@ -551,6 +621,21 @@ uint32_t pm_flat_short_gids(void* handle);
  * count; -4 with 2^24 or more patterns. */
 int pm_flat_expand_matches(void* handle, const uint32_t* gids, size_t n, uint32_t min_len, uint64_t* events,
                            size_t cap, size_t* nevents);
+/* Pattern groups on the host (above).  pm_flat_group_tables: from one mask
+ * per pattern in add order (n = the patterns added), exactly the two arrays
+ * pm_hip_set_groups uploads, n + 1 entries each in gid space with [0] = 0:
+ * gmask[g] the pattern's mask, reach[g] the OR of gmask over g's suffix chain.
+ * Returns 0; -2 for a wrong n or a NULL pointer.
+ * pm_flat_expand_groups: the group list of n dense gids, for either image
+ * kind and either form: position k lies in the stream whose offsets hold it
+ * (offsets[0 .. nseg], non-decreasing; stream_groups NULL = every stream
+ * 0xFFFFFFFF).  Output rules and return codes as pm_flat_expand_matches; -2
+ * also for NULL groups_by_index or offsets that descend. */
+int pm_flat_group_tables(void* handle, const uint32_t* groups_by_index, size_t n, uint32_t* gmask_out,
+                         uint32_t* reach_out);
+int pm_flat_expand_groups(void* handle, const uint32_t* gids, size_t n, const int64_t* offsets, size_t nseg,
+                          const uint32_t* stream_groups, const uint32_t* groups_by_index, uint32_t min_len, int all,
+                          uint64_t* events, size_t cap, size_t* nevents);
 void pm_flat_free(void* handle);
 
 #ifdef __cplusplus

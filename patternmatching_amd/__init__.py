@@ -20,7 +20,10 @@ interface:
                     scan_*_events_device) and, with every pattern that
                     ends at a position, their all-matches forms
                     (HipMatcher.read_*_matches / scan_*_matches_device,
-                    FlowTable.scan_matches)
+                    FlowTable.scan_matches), and their group forms: a group
+                    mask per pattern (HipMatcher.set_groups) and per stream
+                    (HipMatcher.read_*_groups / scan_*_groups_device,
+                    FlowTable.scan_groups)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401

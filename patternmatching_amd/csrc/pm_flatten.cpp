@@ -434,6 +434,48 @@ PmParents pm_build_parents(const std::vector<std::string>& pats, const PmGidMap&
     return r;
 }
 
+PmGroupTables pm_group_tables(const PmGidMap& g, const PmParents& par, const uint32_t* groups_by_index) {
+    const size_t G = g.index_of_gid.size();
+    PmGroupTables t;
+    t.gmask.assign(G, 0);
+    t.reach.assign(G, 0);
+    for (size_t q = 1; q < G; ++q) t.gmask[q] = groups_by_index[g.index_of_gid[q]];
+    // a parent is one level shallower than its child: by depth, parents first
+    std::vector<uint32_t> order(G);
+    for (size_t q = 0; q < G; ++q) order[q] = (uint32_t)q;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return par.depth[a] < par.depth[b]; });
+    for (uint32_t q : order)
+        if (q) t.reach[q] = t.gmask[q] | t.reach[par.parent[q]];
+    return t;
+}
+
+void pm_expand_groups(const PmGidMap& g, const PmParents& par, const PmGroupTables& t, const uint32_t* gids, size_t n,
+                      const int64_t* offsets, size_t nseg, const uint32_t* stream_groups, uint32_t min_len, bool all,
+                      uint64_t* events, size_t cap, size_t* nevents) {
+    size_t total = 0, j = 0;
+    std::vector<uint64_t> one;
+    for (size_t k = 0; k < n && nseg; ++k) {
+        // the stream holding k: the last one that begins at or before k (offsets ascend), below nseg
+        while (j + 1 < nseg && offsets[j + 1] <= (int64_t)k) ++j;
+        uint32_t h = gids[k];
+        if (h == 0 || h >= par.parent.size()) continue;
+        const uint32_t sm = stream_groups ? stream_groups[j] : 0xFFFFFFFFu;
+        one.clear();
+        for (uint32_t d = par.depth[h]; d > 0 && h != 0 && g.len[h] >= min_len && (t.reach[h] & sm);
+             --d, h = par.parent[h]) {
+            if (!(t.gmask[h] & sm)) continue;
+            one.push_back((uint64_t)k << 24 | h);
+            if (!all) break;
+        }
+        std::sort(one.begin(), one.end());
+        for (const uint64_t e : one) {
+            if (total < cap) events[total] = e;
+            ++total;
+        }
+    }
+    *nevents = total;
+}
+
 // The sparse form (pm_flatten.h).  order: states by depth, so a state's
 // failure (shallower) is decided before it.  The fallback of v is fail[v]
 // when that keeps a row, else fail[v]'s own fallback; then delta(v, c) =

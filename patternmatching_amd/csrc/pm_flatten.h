@@ -155,6 +155,28 @@ RtImage pm_build_rt(const std::vector<std::string>& pats, const PmGidMap& g);
 DfaImage pm_build_dfa(const std::vector<std::string>& pats, const PmGidMap& g);
 PmParents pm_build_parents(const std::vector<std::string>& pats, const PmGidMap& g);
 
+// Pattern groups (pm_hip.h, "pattern groups") in gid space, from one u32 mask
+// per pattern in add order: gmask[g] = groups_by_index[index_of_gid[g]] and
+// reach[g] = the OR of gmask over g's suffix chain (g, parent[g], ...), both
+// with [0] = 0.  A byte string added twice: the add that wins (pm_assign_gids)
+// is the one a scan answers and the one on the chains; the shadowed gid keeps
+// its own mask in gmask but is on nobody's chain.
+struct PmGroupTables {
+    std::vector<uint32_t> gmask, reach;
+};
+PmGroupTables pm_group_tables(const PmGidMap& g, const PmParents& par, const uint32_t* groups_by_index);
+
+// The group match list of n dense gids on the host (the contract of the group
+// kernels): position k lies in stream j = (first offsets[] entry above k) - 1,
+// clamped into [0, nseg); its events are the members h of gids[k]'s chain with
+// len[h] >= min_len and gmask[h] & stream_groups[j] -- all of them, or the
+// first one only.  stream_groups null: every stream 0xFFFFFFFF.  Positions
+// ascend, a position's events ascend by gid; *nevents = the total, the first
+// min(cap, total) are stored.  A gid out of range counts as no match.
+void pm_expand_groups(const PmGidMap& g, const PmParents& par, const PmGroupTables& t, const uint32_t* gids, size_t n,
+                      const int64_t* offsets, size_t nseg, const uint32_t* stream_groups, uint32_t min_len, bool all,
+                      uint64_t* events, size_t cap, size_t* nevents);
+
 // The sparse form with 8-B record units (a device layout, built from the
 // 16-B form at compile time; not cached): rows [0, F) as before, then the
 // records in the same order, each at a unit offset u with state id F + u:

@@ -170,6 +170,29 @@ hipError_t pm_launch_dfa_flows_matches(const uint8_t* text, const int64_t* offse
                                        const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
                                        const MatchDev& mx, const DfaDev& t, uint32_t states, int64_t force_seg,
                                        int num_cu, hipStream_t s);
+// What the group forms add (pm_hip.h, "pattern groups"): gmask[g], the group
+// mask of pattern g, and reach[g], the OR of gmask over g's suffix chain
+// (n_patterns + 1 entries each, [0] = 0; pm_group_tables), and the streams'
+// masks: nseg values, nullptr = every stream 0xFFFFFFFF.
+struct GroupDev {
+    const uint32_t* gmask;
+    const uint32_t* reach;
+    const uint32_t* stream_groups;
+};
+// pm_launch_rt_batch_matches / pm_launch_dfa_flows_matches restricted to the
+// patterns visible to a position's stream, gmask[h] & stream_groups[j] != 0
+// (rt_batch_groups_kernel, dfa_flow_groups_kernel).  all: every visible
+// member of the chain with at least min_len bytes; else the first one, which
+// is the answer of a matcher compiled from the visible patterns alone.
+// Arguments, launch shapes and memory safety are the siblings'; the stream
+// index a mask is read at is clamped into [0, nseg).
+hipError_t pm_launch_rt_batch_groups(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                     const EvDev& ev, const MatchDev& mx, const GroupDev& gr, bool all,
+                                     const RtDev& t, int num_cu, hipStream_t s);
+hipError_t pm_launch_dfa_flows_groups(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                      const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
+                                      const MatchDev& mx, const GroupDev& gr, bool all, const DfaDev& t,
+                                      uint32_t states, int64_t force_seg, int num_cu, hipStream_t s);
 // The sparse kernel (PmSparseKernel) a launch of this width runs, 0 when
 // it runs dense rows: the forced DfaDev::sparse_kernel where the object
 // and width allow it, else the product choice.

@@ -2338,6 +2338,305 @@ __global__ __launch_bounds__(DFA_THREADS) void dfa_flow_matches_kernel(
             if (offs[j + 1] <= offs[j]) state_out[j] = load_state(j);
 }
 
+// ---- pattern groups: the match list of the patterns a stream is scanned for ---
+// The group forms of the two all-matches kernels (pm_hip.h, "pattern
+// groups"): pattern h is visible to stream j iff gmask[h] & stream_groups[j],
+// and position i of stream j emits the visible members of its answer's chain
+// that pass ev_keep -- all of them (ALL), or the first one only, which is what
+// a matcher compiled from the visible patterns alone answers at i.  They are
+// kernels of their own for the reason given above: the matches kernels' text
+// with the mask tests added, everything up to a step's heads unchanged.
+// A chain member now has two bits that are kept apart.  pending: the chain
+// goes on below it; it ends on ev_keep (the length test, gid 0) only, never
+// on an invisible member -- or where reach[h], the OR of gmask over h's whole
+// chain, misses the stream's mask: nothing further down is visible.  emit:
+// the member itself is visible.  A slot may be pending without emitting, in
+// the head's round too; with ALL == false the first emit ends the chain.
+// The rejects before any walk: ev_keep(g) as before (with min_len >= 3 the
+// compare with n_short: the whole chain is short then), and only a survivor
+// loads reach[g] -- one dword from a table of a few hundred KiB at most.
+// The stream's mask.  The flow kernel's lanes track j and load the mask where
+// j is set; a step's heads are filtered after the end-of-stream update may
+// have moved j on, so the step keeps the mask it began with (sm0: a step's
+// positions lie in one stream).  A lane of the batched kernel knows its
+// stream's start, not j.  Where no stream begins between the tile's first
+// byte and the lane, j is a - 1: one wave-uniform load per wave that holds a
+// survivor of ev_keep.  Else the survivor searches the tile's offsets [a, b]
+// for the first one above i (flow_seek, per lane), minus one; a run of empty
+// streams shares an offset and the search lands on the last of the run, the
+// one that holds the byte.  The index is clamped into [0, nseg), so no mask
+// is read out of bounds whatever the offsets hold, and gmask / reach are read
+// at gids below n_patterns + 1 like parent[] and len[].
+// A wave with a survivor waits for memory where its matches sibling stages
+// the head at once, so what a member needs is asked for together: reach and
+// gmask of a member in one go, in the batched kernel with the first stream's
+// mask, and only for a parent that passes ev_keep (most chains end there, at
+// gid 0, with no table load); the flow kernel asks for eight heads' entries
+// at a time.  Two variants of the batched kernel were built and measured
+//  and are not kept: the stream index staged per
+// boundary bit in LDS (4 KiB, written by the pass that sets s_mask) in place
+// of the search, and the parent asked for one round ahead; both were slower
+// on the 1,500-byte ASCII cells.
+// Rounds, ranking and reservations are the matches kernels': every ev_reserve
+// is reached from wave-uniform control flow, the rounds are bounded by
+// max_depth.
+template <bool SMALL, bool ALL>
+__global__ __launch_bounds__(RT_THREADS) void rt_batch_groups_kernel(const uint8_t* __restrict__ text,
+                                                                     const int64_t* __restrict__ offs, int64_t nseg,
+                                                                     int64_t n, EvDev ev, MatchDev mx, GroupDev gr,
+                                                                     RtDev t) {
+    constexpr int kT12Words = SMALL ? 0 : RT_T2_U16 / 2;
+    constexpr int kStageWords = (RT_THREADS / 64) * RT_EV_STAGE * 2;
+    __shared__ __attribute__((aligned(16))) uint32_t s_lds[kT12Words + kStageWords + RT_BATCH_TILE / 32];
+    uint32_t* const s_mask = s_lds + kT12Words + kStageWords;
+    const uint16_t* s_t = t.t12;
+    const int tid = threadIdx.x;
+    EvWave<RT_EV_STAGE> stage{reinterpret_cast<uint64_t*>(s_lds + kT12Words) + (tid >> 6) * RT_EV_STAGE, 0u};
+    if (!SMALL) {
+        const uint4* src = reinterpret_cast<const uint4*>(t.t12);
+        uint4* dst = reinterpret_cast<uint4*>(s_lds);
+        for (int k = tid; k < RT_T2_U16 * 2 / 16; k += RT_THREADS) dst[k] = src[k];
+        __syncthreads();
+        s_t = reinterpret_cast<const uint16_t*>(s_lds);
+    }
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t T0 = ntiles * (int64_t)blockIdx.x / (int64_t)gridDim.x;
+    const int64_t T1 = ntiles * ((int64_t)blockIdx.x + 1) / (int64_t)gridDim.x;
+    const int64_t noffs = nseg + 1;
+    int64_t a = batch_seek(offs, 0, noffs, T0 * RT_BATCH_TILE + 1);
+    for (int64_t T = T0; T < T1; ++T) {
+        const int64_t base = T * RT_BATCH_TILE;
+        const int64_t end = base + RT_BATCH_TILE < n ? base + RT_BATCH_TILE : n;
+        a = batch_seek(offs, a, noffs, base + 1);
+        const int64_t b = batch_seek(offs, a, noffs, end);
+        int64_t start = a > 0 ? (int64_t)rfl64((uint64_t)offs[a - 1]) : 0;
+        bool first = true;  // no stream begins in (base, i]: the lane's stream is a - 1, the tile's first
+        if (b > a) {  // workgroup-uniform
+            __syncthreads();
+            if (tid < RT_BATCH_TILE / 32) s_mask[tid] = 0u;
+            __syncthreads();
+            for (int64_t j = a + tid; j < b; j += RT_THREADS) {
+                const int64_t rel = offs[j] - base;
+                if (rel > 0 && rel < RT_BATCH_TILE) atomicOr(&s_mask[rel >> 5], 1u << (rel & 31));
+            }
+            __syncthreads();
+            int w = tid >> 5;
+            uint32_t m = s_mask[w] & (0xFFFFFFFFu >> (31 - (tid & 31)));
+            while (!m && w > 0) m = s_mask[--w];
+            if (m) {
+                start = base + w * 32 + 31 - __clz(m);
+                first = false;
+            }
+        }
+        const int64_t i = base + tid;
+        uint32_t v = 0;
+        if (i < n) {
+            start = start < 0 ? 0 : start > i ? i : start;
+            v = rt_one(text, s_t, t, i, start);
+        }
+        // all 64 lanes of every wave are here (a lane past n holds v = 0)
+        uint32_t h = 0u;  // the lane's pending chain member, 0 = done
+        bool emit = false;  // h is visible to the lane's stream
+        uint32_t sm = 0xFFFFFFFFu;
+        const bool k0 = ev_keep(v, ev);
+        if (__ballot(k0)) {  // wave-uniform: one wave in 20 on random ASCII
+            // three loads in flight at once, not one after the other: the mask of the tile's
+            // first stream (a wave-uniform address) and the head's two table entries
+            if (gr.stream_groups) sm = gr.stream_groups[a < 1 ? 0 : a > nseg ? nseg - 1 : a - 1];
+            if (k0) {
+                const uint32_t rc = gr.reach[v], gm = gr.gmask[v];
+                if (gr.stream_groups && !first) {
+                    // the stream holding i: the first offset > i, minus one; offs[a - 1] <= base, offs[b] >= end
+                    int64_t j = flow_seek(offs, a, b + 1 < noffs ? b + 1 : noffs, i + 1) - 1;
+                    j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+                    sm = gr.stream_groups[j];
+                }
+                if (rc & sm) {
+                    h = v;
+                    emit = (gm & sm) != 0u;
+                }
+            }
+        }
+        if (__ballot(h != 0u)) {
+            for (uint32_t d = 0;;) {  // wave-uniform; round 0 is the heads'
+                const uint64_t em = __ballot(emit);
+                if (em) {
+                    const EvSlot slot = ev_reserve(stage, (uint32_t)__popcll(em), ev);
+                    if (emit) ev_put(stage, slot, wave_prefix(em), (uint64_t)i << PM_EV_GID_BITS | h, ev);
+                }
+                if (!ALL && emit) h = 0u;
+                if (++d >= mx.max_depth) break;
+                emit = false;
+                if (h) {
+                    const uint32_t p = mx.parent[h];
+                    h = 0u;
+                    if (ev_keep(p, ev)) {  // most chains end here (gid 0), with no table load
+                        const uint32_t rc = gr.reach[p], gm = gr.gmask[p];
+                        if (rc & sm) {
+                            h = p;
+                            emit = (gm & sm) != 0u;
+                        }
+                    }
+                }
+                if (!__ballot(h != 0u)) break;
+            }
+        }
+        a = b;
+    }
+    ev_flush(stage, ev);
+}
+
+template <bool CODED, bool ALL>
+__global__ __launch_bounds__(DFA_THREADS) void dfa_flow_groups_kernel(
+    const uint8_t* __restrict__ text, const int64_t* __restrict__ offs, int64_t nseg, int64_t n,
+    const uint32_t* __restrict__ state_in, uint32_t* __restrict__ state_out, EvDev ev, MatchDev mx, GroupDev gr,
+    const uint32_t* __restrict__ nxt, const uint32_t* __restrict__ outt, uint32_t states, int64_t warm,
+    int64_t seg_len, const uint32_t* __restrict__ gram3) {
+    __shared__ uint64_t s_stage[(DFA_THREADS / 64) * DFA_EV_STAGE];
+    EvWave<DFA_EV_STAGE> stage{s_stage + (threadIdx.x >> 6) * DFA_EV_STAGE, 0u};
+    const int64_t nlane = (n + seg_len - 1) / seg_len;
+    const int64_t stride = (int64_t)gridDim.x * DFA_THREADS;
+    const int64_t gtid = (int64_t)blockIdx.x * DFA_THREADS + threadIdx.x;
+    const int64_t noffs = nseg + 1;
+    auto load_state = [&](int64_t j) -> uint32_t {  // j in [0, nseg)
+        const uint32_t s = state_in ? state_in[j] : 0u;
+        return s < states ? s : 0u;
+    };
+    auto load_mask = [&](int64_t j) -> uint32_t {  // j in [0, nseg)
+        return gr.stream_groups ? gr.stream_groups[j] : 0xFFFFFFFFu;
+    };
+    for (int64_t sg0 = gtid - (threadIdx.x & 63); sg0 < nlane; sg0 += stride) {  // wave-uniform
+        const int64_t sg = sg0 + (threadIdx.x & 63);
+        int64_t i = 0, hi = 0, end = 0, j = 0;  // a lane without a segment: no step
+        uint32_t s = 0, sm = 0;
+        if (sg < nlane) {
+            const int64_t lo = sg * seg_len;
+            hi = lo + seg_len < n ? lo + seg_len : n;
+            // the stream holding lo: the first offset > lo, minus one
+            j = flow_seek(offs, 0, noffs, lo + 1) - 1;
+            j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+            int64_t start = offs[j];
+            start = start < 0 ? 0 : start > lo ? lo : start;
+            end = offs[j + 1];
+            sm = load_mask(j);
+            int64_t wlo = lo - warm;
+            if (wlo < start) wlo = start;
+            int64_t w = wlo;
+            if (gram3) w = dfa_sync_lo(text, lo, wlo, gram3);  // in [wlo, lo]: never before start
+            s = (w == wlo && wlo == start) ? load_state(j) : 0u;
+            for (int64_t k = w; k < lo; ++k) {
+                const uint32_t v = nxt[(size_t)s * 256 + text[k]];
+                s = CODED ? v & DFA_STATE_MASK : v;
+            }
+            i = lo;
+        }
+        while (__any(i < hi)) {  // wave-uniform: one step of every lane that has positions left
+            const int64_t p0 = i;
+            const uint32_t sm0 = sm;  // the mask of the stream this step's positions lie in
+            uint32_t r[16];
+            uint32_t keep = 0;  // bit q: position p0 + q has a pending chain member r[q]
+            if (i < hi) {
+                if ((i & 15) == 0 && i + 16 <= hi && i + 16 <= end) {
+                    const uint4 tw = *reinterpret_cast<const uint4*>(text + i);
+                    const uint32_t W[4] = {tw.x, tw.y, tw.z, tw.w};
+                    uint32_t st[16];
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const uint32_t v = nxt[(size_t)s * 256 + ((W[q >> 2] >> (8 * (q & 3))) & 0xFFu)];
+                        s = CODED ? v & DFA_STATE_MASK : v;
+                        r[q] = CODED ? v >> 20 : 0u;
+                        st[q] = s;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        if (CODED) r[q] = r[q] == DFA_ESC ? outt[st[q]] : r[q];
+                        else r[q] = outt[st[q]];
+                        keep |= (uint32_t)ev_keep(r[q], ev) << q;
+                    }
+                    i += 16;
+                } else {
+                    const uint32_t v = nxt[(size_t)s * 256 + text[i]];
+                    s = CODED ? v & DFA_STATE_MASK : v;
+                    uint32_t id = CODED ? v >> 20 : outt[s];
+                    if (CODED && id == DFA_ESC) id = outt[s];
+                    r[0] = id;
+                    keep = (uint32_t)ev_keep(id, ev);
+                    ++i;
+                }
+                if (i == end) {  // position end - 1 was stream j's last byte
+                    if (state_out) state_out[j] = s;
+                    if (i < hi) {
+                        // the next stream that is not empty: the first offset > i, minus one
+                        j = flow_seek(offs, j + 2 < noffs ? j + 2 : noffs, noffs, i + 1) - 1;
+                        j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+                        end = offs[j + 1];
+                        s = load_state(j);
+                        sm = load_mask(j);
+                    }
+                }
+            }
+            uint32_t emit = 0;  // bit q: r[q] is visible to the step's stream
+            // the heads that passed ev_keep: reach, and the head's own mask.  Eight positions'
+            // loads are asked for together (a slot without a head reads entry 0), so a step
+            // waits for memory once per half, not once per head.
+#pragma unroll
+            for (int q0 = 0; q0 < 16; q0 += 8)
+                if ((keep >> q0) & 0xFFu) {
+                    uint32_t rc[8], gm[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const uint32_t g = (keep >> (q0 + q)) & 1u ? r[q0 + q] : 0u;
+                        rc[q] = gr.reach[g];
+                        gm[q] = gr.gmask[g];
+                    }
+#pragma unroll
+                    for (int q = 0; q < 8; ++q)
+                        if ((keep >> (q0 + q)) & 1u) {
+                            if (!(rc[q] & sm0)) keep &= ~(1u << (q0 + q));
+                            else if (gm[q] & sm0) emit |= 1u << (q0 + q);
+                        }
+                }
+            // all 64 lanes are here
+            if (__any(keep != 0u)) {
+                for (uint32_t d = 0;;) {  // wave-uniform; round 0 is the heads'
+                    if (__any(emit != 0u)) {
+                        const uint32_t c = __popc(emit);
+                        const uint32_t incl = wave_scan_incl(c);
+                        const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
+                        const EvSlot slot = ev_reserve(stage, total, ev);
+                        uint32_t k = incl - c;
+#pragma unroll
+                        for (int q = 0; q < 16; ++q)
+                            if ((emit >> q) & 1u)
+                                ev_put(stage, slot, k++, (uint64_t)(p0 + q) << PM_EV_GID_BITS | r[q], ev);
+                    }
+                    if (!ALL) keep &= ~emit;
+                    if (++d >= mx.max_depth) break;
+                    emit = 0;
+                    // r[q] = parent[r[q]] in place; a member that fails the filter ends its chain
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if ((keep >> q) & 1u) {
+                            const uint32_t h = mx.parent[r[q]];
+                            const uint32_t rc = gr.reach[h], gm = gr.gmask[h];
+                            if (ev_keep(h, ev) && (rc & sm0)) {
+                                r[q] = h;
+                                if (gm & sm0) emit |= 1u << q;
+                            } else {
+                                keep &= ~(1u << q);
+                            }
+                        }
+                    if (!__any(keep != 0u)) break;
+                }
+            }
+        }
+    }
+    ev_flush(stage, ev);
+    if (state_out)  // empty streams keep their state (as used: an invalid one is the root)
+        for (int64_t j = gtid; j < nseg; j += stride)
+            if (offs[j + 1] <= offs[j]) state_out[j] = load_state(j);
+}
+
 // The sparse (default-transition) form, pm_flatten.h: rows only for the
 // states whose row differs from their fallback's in more than PM_SDFA_K
 // bytes, 16-B records for the rest (8-B units in pm_pack_sparse8's
@@ -3610,6 +3909,24 @@ hipError_t pm_launch_rt_batch_matches(const uint8_t* text, const int64_t* offset
     return hipGetLastError();
 }
 
+// Its group form (rt_batch_groups_kernel): the same launch.
+hipError_t pm_launch_rt_batch_groups(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                     const EvDev& ev, const MatchDev& mx, const GroupDev& gr, bool all,
+                                     const RtDev& t, int num_cu, hipStream_t s) {
+    if (n <= 0 || nseg <= 0) return hipSuccess;
+    if (!text || !offsets || num_cu <= 0) return hipErrorInvalidValue;
+    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent || !gr.gmask || !gr.reach)
+        return hipErrorInvalidValue;
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
+    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
+    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    auto* const k = small ? (all ? rt_batch_groups_kernel<true, true> : rt_batch_groups_kernel<true, false>)
+                          : (all ? rt_batch_groups_kernel<false, true> : rt_batch_groups_kernel<false, false>);
+    hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, ev, mx, gr, t);
+    return hipGetLastError();
+}
+
 hipError_t pm_launch_rt_serve(PmServeReq* req, uint64_t* fwd, uint32_t* done, int blocks, uint64_t seen,
                               uint64_t gen, int64_t idle_ticks, const RtDev& t, hipStream_t s) {
     if (blocks <= 0) return hipErrorInvalidValue;
@@ -3882,6 +4199,27 @@ hipError_t pm_launch_dfa_flows_matches(const uint8_t* text, const int64_t* offse
     else
         hipLaunchKernelGGL(dfa_flow_matches_kernel<false>, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev,
                            mx, t.next, t.out, states, t.warm, seg, g3);
+    return hipGetLastError();
+}
+
+// Its group form (dfa_flow_groups_kernel): the same launch.
+hipError_t pm_launch_dfa_flows_groups(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                      const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
+                                      const MatchDev& mx, const GroupDev& gr, bool all, const DfaDev& t,
+                                      uint32_t states, int64_t force_seg, int num_cu, hipStream_t s) {
+    if (nseg <= 0 || n < 0 || (n == 0 && !state_out)) return hipSuccess;
+    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
+    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent || !gr.gmask || !gr.reach)
+        return hipErrorInvalidValue;
+    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
+    int64_t seg, blocks;
+    if (!flow_shape(nseg, n, 16, force_seg, num_cu, seg, blocks)) return hipErrorInvalidValue;
+    const dim3 g((unsigned)blocks), b(DFA_THREADS);
+    const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
+    auto* const k = t.coded ? (all ? dfa_flow_groups_kernel<true, true> : dfa_flow_groups_kernel<true, false>)
+                            : (all ? dfa_flow_groups_kernel<false, true> : dfa_flow_groups_kernel<false, false>);
+    hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev, mx, gr, t.next, t.out, states,
+                       t.warm, seg, g3);
     return hipGetLastError();
 }
 

@@ -258,6 +258,9 @@ struct BatchStage {
     uint64_t* d_ev = nullptr;
     unsigned long long* d_nev = nullptr;
     size_t cap_ev = 0;
+    // the group calls' stream masks (pm_hip_read_*_groups), cap_grp of them
+    uint32_t* d_grp = nullptr;
+    size_t cap_grp = 0;
     hipStream_t s = nullptr;
 };
 struct PmHip {
@@ -278,6 +281,11 @@ struct PmHip {
     const uint32_t* d_len = nullptr;  // PmGidMap::len (the events kernels' filter)
     uint32_t max_depth = 0;           // the largest depth[]: bounds the all-matches kernels' chain walk
     std::vector<uint32_t> parent;
+    // pattern groups (pm_hip_set_groups): nothing before its first call
+    std::vector<uint32_t> depth;  // PmParents::depth, for pm_group_tables
+    std::vector<uint32_t> gmask;  // host copy of d_gmask (pm_hip_pattern_groups)
+    uint32_t* d_gmask = nullptr;  // in allocs
+    uint32_t* d_reach = nullptr;
     std::string cache_dir;   // compiled-image cache (else $PM_IMAGE_CACHE)
     bool cache_hit = false;
     std::vector<void*> allocs;
@@ -1308,6 +1316,7 @@ void pm_hip_compile(void* obj) {
     o->d_depth = (const uint32_t*)dalloc_copy(o, im.par.depth.data(), im.par.depth.size() * 4);
     o->max_depth = im.par.depth.empty() ? 0u : *std::max_element(im.par.depth.begin(), im.par.depth.end());
     o->parent = std::move(im.par.parent);
+    o->depth = std::move(im.par.depth);
     o->d_len = (const uint32_t*)dalloc_copy(o, o->gids.len.data(), o->gids.len.size() * 4);
     o->id_of_gid.assign(o->gids.index_of_gid.size(), PM_NULL_PATTERN_ID);
     for (size_t g = 1; g < o->gids.index_of_gid.size(); ++g) o->id_of_gid[g] = o->ids[o->gids.index_of_gid[g]];
@@ -1384,6 +1393,7 @@ void pm_hip_free(void* obj) {
     if (o->batch.d_st_out) (void)hipFree(o->batch.d_st_out);
     if (o->batch.d_ev) (void)hipFree(o->batch.d_ev);
     if (o->batch.d_nev) (void)hipFree(o->batch.d_nev);
+    if (o->batch.d_grp) (void)hipFree(o->batch.d_grp);
     if (o->batch.s) (void)hipStreamDestroy(o->batch.s);
     free_pick(o->pick);
     for (PipeSlot& q : o->slot) {
@@ -1788,6 +1798,26 @@ static EvDev events_dev(PmHip* o, uint32_t min_len, uint64_t* d_events, uint64_t
 
 static MatchDev matches_dev(PmHip* o) { return MatchDev{o->d_parent, o->max_depth}; }
 
+// -7 before pm_hip_set_groups: a group scan has no tables to read.
+static int groups_check(PmHip* o) {
+    if (!o->d_gmask) {
+        std::snprintf(g_err, sizeof(g_err), "pm_hip_set_groups was not called: a group scan needs the group tables");
+        return -7;
+    }
+    return 0;
+}
+
+static GroupDev groups_dev(PmHip* o, const uint32_t* d_stream_groups) {
+    return GroupDev{o->d_gmask, o->d_reach, d_stream_groups};
+}
+
+// What the host group forms add to read_events: the streams' masks (host,
+// nseg of them; null = every stream 0xFFFFFFFF) and the form.
+struct GroupArgs {
+    const uint32_t* stream_groups;
+    bool all;
+};
+
 // The batched events call; all: an event for every pattern ending at a
 // position (pm_hip_scan_batch_matches_device), not only the longest.
 static int scan_batch_events(PmHip* o, bool all, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
@@ -1895,8 +1925,11 @@ uint32_t pm_hip_pattern_len(void* obj, uint32_t gid) {
 // the first launch changed nothing the second reads).  Then only the events
 // come back, are sorted, and the first min(cap, total) handed over.
 // Everything is checked before anything is written.
+// ga (the group forms, pm_hip_read_*_groups): the streams' masks are staged
+// beside the offsets and the group kernels launched; `all` is then ga->all.
 static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
-                       uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents) {
+                       uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents,
+                       const GroupArgs* ga = nullptr) {
     if (const int rc = flows ? flows_check(o) : batch_check(o)) return rc;
     bool ok = (nseg == 0 || offsets) && nseg < ((size_t)1 << 60);
     if (ok && nseg) {
@@ -1916,6 +1949,8 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
                                          nevents, false))
         return rc;
     if (const int rc = events_gid_check(o)) return rc;
+    if (ga)
+        if (const int rc = groups_check(o)) return rc;
     *nevents = 0;
     if (n == 0) return 0;  // the flow form: every stream keeps its state, which the caller's array holds
     PM_CHECK(hipSetDevice(o->device));
@@ -1932,11 +1967,22 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         PM_CHECK(hipMalloc(&q.d_st_out, c * sizeof(uint32_t)));
         q.cap_st = c;
     }
+    const bool grp = ga && ga->stream_groups;
+    if (grp && nseg > q.cap_grp) {
+        if (q.d_grp) PM_CHECK(hipFree(q.d_grp));
+        q.d_grp = nullptr;
+        q.cap_grp = 0;
+        const size_t c = std::max(nseg, (size_t)1 << 10);
+        PM_CHECK(hipMalloc(&q.d_grp, c * sizeof(uint32_t)));
+        q.cap_grp = c;
+    }
     if (!q.d_nev) PM_CHECK(hipMalloc(&q.d_nev, sizeof(unsigned long long)));
     serve_stop(o);  // a device launch wants the whole device
     PM_CHECK(hipMemcpyAsync(q.d_text, buf, n, hipMemcpyHostToDevice, q.s));
     PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
     if (st) PM_CHECK(hipMemcpyAsync(q.d_st_in, state, nseg * sizeof(uint32_t), hipMemcpyHostToDevice, q.s));
+    if (grp)
+        PM_CHECK(hipMemcpyAsync(q.d_grp, ga->stream_groups, nseg * sizeof(uint32_t), hipMemcpyHostToDevice, q.s));
     size_t dcap = o->events_cap > 0 ? (size_t)o->events_cap : std::max<size_t>(1024, n / 16);
     unsigned long long total = 0;
     for (int launch = 0; launch < 2; ++launch) {
@@ -1953,7 +1999,14 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         const uint32_t* const si = st ? q.d_st_in : nullptr;
         uint32_t* const so = st ? q.d_st_out : nullptr;
         hipError_t e;
-        if (all)
+        if (ga) {
+            const GroupDev gr = groups_dev(o, grp ? q.d_grp : nullptr);
+            e = flows ? pm_launch_dfa_flows_groups(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev,
+                                                   matches_dev(o), gr, ga->all, o->dfa, o->dfa_states, o->flow_seg,
+                                                   o->num_cu, q.s)
+                      : pm_launch_rt_batch_groups(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, matches_dev(o), gr,
+                                                  ga->all, o->rt, o->num_cu, q.s);
+        } else if (all)
             e = flows ? pm_launch_dfa_flows_matches(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev,
                                                     matches_dev(o), o->dfa, o->dfa_states, o->flow_seg, o->num_cu, q.s)
                       : pm_launch_rt_batch_matches(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, matches_dev(o),
@@ -1966,7 +2019,7 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(q.s);
             std::snprintf(g_err, sizeof(g_err), "%s %s launch: %s", flows ? "flow" : "batch",
-                          all ? "matches" : "events", hipGetErrorString(e));
+                          ga ? "groups" : all ? "matches" : "events", hipGetErrorString(e));
             return -3;
         }
         PM_CHECK(hipMemcpyAsync(&total, q.d_nev, sizeof(total), hipMemcpyDeviceToHost, q.s));
@@ -2005,6 +2058,121 @@ int pm_hip_read_flows_events(void* obj, const uint8_t* buf, const int64_t* offse
 int pm_hip_read_flows_matches(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                               uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents) {
     return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents);
+}
+
+// ---- pattern groups (pm_hip.h, "pattern groups") -----------------------------
+// The two tables of pm_group_tables on the device.  The first call allocates
+// them (from then on they count in pm_hip_table_bytes); a later one is a rule
+// reload: the same buffers, overwritten after a device synchronize.
+int pm_hip_set_groups(void* obj, const uint32_t* groups, size_t n) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    if (!groups || n != o->pats.size()) {
+        std::snprintf(g_err, sizeof(g_err), "bad arguments (groups required, n == the %zu patterns added)",
+                      o->pats.size());
+        return -2;
+    }
+    PmParents par;
+    par.parent = o->parent;
+    par.depth = o->depth;
+    PmGroupTables t = pm_group_tables(o->gids, par, groups);
+    PM_CHECK(hipSetDevice(o->device));
+    const size_t bytes = t.gmask.size() * sizeof(uint32_t);
+    if (!o->d_gmask) {
+        o->d_gmask = (uint32_t*)dalloc_copy(o, t.gmask.data(), bytes);
+        o->d_reach = (uint32_t*)dalloc_copy(o, t.reach.data(), bytes);
+    } else {
+        PM_CHECK(hipDeviceSynchronize());  // the caller has no group scan in flight; nor has this object now
+        PM_CHECK(hipMemcpy(o->d_gmask, t.gmask.data(), bytes, hipMemcpyHostToDevice));
+        PM_CHECK(hipMemcpy(o->d_reach, t.reach.data(), bytes, hipMemcpyHostToDevice));
+    }
+    o->gmask = std::move(t.gmask);
+    return 0;
+}
+
+uint32_t pm_hip_pattern_groups(void* obj, uint32_t gid) {
+    PmHip* o = as(obj);
+    return gid < o->gmask.size() ? o->gmask[gid] : 0u;
+}
+
+int pm_hip_scan_batch_groups_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_stream_groups, uint32_t min_len, int all,
+                                    uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                    void* hip_stream) {
+    PmHip* o = as(obj);
+    if (const int rc = batch_check(o)) return rc;
+    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) ||
+        ((uintptr_t)d_stream_groups & 3) || (nseg > 0 && n > 0 && (!d_text || !d_offsets))) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned, stream groups 4-B "
+                      "aligned)");
+        return -2;
+    }
+    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
+    if (const int rc = events_gid_check(o)) return rc;
+    if (const int rc = groups_check(o)) return rc;
+    if (nseg == 0 || n == 0) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess)
+        e = pm_launch_rt_batch_groups(d_text, d_offsets, nseg, n, events_dev(o, min_len, d_events, cap, d_nevents),
+                                      matches_dev(o), groups_dev(o, d_stream_groups), all != 0, o->rt, o->num_cu,
+                                      (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "batch groups launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_RT;
+    o->last_form = 0;
+    return 0;
+}
+
+int pm_hip_scan_flows_groups_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out,
+                                    const uint32_t* d_stream_groups, uint32_t min_len, int all, uint64_t* d_events,
+                                    uint64_t cap, unsigned long long* d_nevents, void* hip_stream) {
+    PmHip* o = as(obj);
+    if (const int rc = flows_check(o)) return rc;
+    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_state_in & 3) ||
+        ((uintptr_t)d_state_out & 3) || ((uintptr_t)d_stream_groups & 3) ||
+        (d_state_in && d_state_in == d_state_out) || (nseg > 0 && (!d_offsets || (n > 0 && !d_text)))) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned, states and stream "
+                      "groups 4-B aligned, state_in != state_out)");
+        return -2;
+    }
+    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
+    if (const int rc = events_gid_check(o)) return rc;
+    if (const int rc = groups_check(o)) return rc;
+    if (nseg == 0 || (n == 0 && !d_state_out)) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess)
+        e = pm_launch_dfa_flows_groups(d_text, d_offsets, nseg, n, d_state_in, d_state_out,
+                                       events_dev(o, min_len, d_events, cap, d_nevents), matches_dev(o),
+                                       groups_dev(o, d_stream_groups), all != 0, o->dfa, o->dfa_states, o->flow_seg,
+                                       o->num_cu, (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "flow groups launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_AC;
+    o->last_form = 1;
+    return 0;
+}
+
+int pm_hip_read_batch_groups(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg,
+                             const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
+                             size_t* nevents) {
+    const GroupArgs ga{stream_groups, all != 0};
+    return read_events(as(obj), false, true, buf, offsets, nseg, nullptr, min_len, events, cap, nevents, &ga);
+}
+
+int pm_hip_read_flows_groups(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                             const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
+                             size_t* nevents) {
+    const GroupArgs ga{stream_groups, all != 0};
+    return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents, &ga);
 }
 
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,
@@ -2063,6 +2231,7 @@ size_t pm_hip_scratch_bytes(void* obj) {
     if (o->batch.d_offs) b += o->batch.cap_offs * sizeof(int64_t);
     if (o->batch.d_st_in) b += 2 * o->batch.cap_st * sizeof(uint32_t);
     if (o->batch.d_ev) b += o->batch.cap_ev * sizeof(uint64_t) + sizeof(unsigned long long);
+    if (o->batch.d_grp) b += o->batch.cap_grp * sizeof(uint32_t);
     return b;
 }
 
@@ -2468,6 +2637,33 @@ int pm_flat_expand_matches(void* handle, const uint32_t* gids, size_t n, uint32_
         }
     }
     *nevents = total;
+    return 0;
+}
+
+// The two tables pm_hip_set_groups uploads, from the same builder.
+int pm_flat_group_tables(void* handle, const uint32_t* groups_by_index, size_t n, uint32_t* gmask_out,
+                         uint32_t* reach_out) {
+    PmFlatHandle* h = static_cast<PmFlatHandle*>(handle);
+    if (!groups_by_index || n != h->g.gid_of_index.size() || !gmask_out || !reach_out) return -2;
+    const PmGroupTables t = pm_group_tables(h->g, h->par, groups_by_index);
+    std::memcpy(gmask_out, t.gmask.data(), t.gmask.size() * sizeof(uint32_t));
+    std::memcpy(reach_out, t.reach.data(), t.reach.size() * sizeof(uint32_t));
+    return 0;
+}
+
+// The group kernels' contract over n dense gids on the host (pm_expand_groups).
+int pm_flat_expand_groups(void* handle, const uint32_t* gids, size_t n, const int64_t* offsets, size_t nseg,
+                          const uint32_t* stream_groups, const uint32_t* groups_by_index, uint32_t min_len, int all,
+                          uint64_t* events, size_t cap, size_t* nevents) {
+    PmFlatHandle* h = static_cast<PmFlatHandle*>(handle);
+    if (min_len == 0 || n > ((size_t)1 << 40) || !nevents || (n && !gids) || (cap && !events) || !groups_by_index ||
+        (nseg && !offsets))
+        return -2;
+    for (size_t j = 0; j < nseg; ++j)
+        if (offsets[j] > offsets[j + 1]) return -2;
+    if (h->par.parent.size() > ((size_t)1 << 24)) return -4;  // a gid has an event's low 24 bits
+    const PmGroupTables t = pm_group_tables(h->g, h->par, groups_by_index);
+    pm_expand_groups(h->g, h->par, t, gids, n, offsets, nseg, stream_groups, min_len, all != 0, events, cap, nevents);
     return 0;
 }
 

@@ -190,6 +190,17 @@ class FlowTable:
         there.  The flows' states advance exactly as in scan()."""
         return self._scan_list(packets, min_len, self.matcher.read_flows_matches, "scan_matches")
 
+    def scan_groups(self, packets, min_len=3, all_matches=True):
+        """scan_matches() with a group mask per packet: packets is a list of
+        (key, bytes-like, groups), and a packet's list holds the patterns
+        visible to it only (HipMatcher.read_flows_groups).  The flows' states
+        advance exactly as in scan(), whatever the masks."""
+        grp = np.array([g for _, _, g in packets], dtype=np.uint32)
+
+        def read(data, offs, state, min_len):
+            return self.matcher.read_flows_groups(data, offs, grp, state, min_len, all_matches)
+        return self._scan_list([(k, b) for k, b, _ in packets], min_len, read, "scan_groups")
+
     def _scan_list(self, packets, min_len, read, name):
         keys = [k for k, _ in packets]
         if len(set(keys)) != len(keys):
@@ -419,11 +430,12 @@ class HipMatcher:
         if rc != 0:
             raise RuntimeError(self.lib.pm_hip_last_error().decode())
 
-    def _read_events(self, data, offsets, state, min_len, all_matches=False):
-        """The host events forms (all_matches: the *_matches ones): (events
-        u64 ascending, state_out or None).  A host buffer too short for the
-        call's events means one more call with room for all of them, from
-        the same states."""
+    def _read_events(self, data, offsets, state, min_len, all_matches=False, stream_groups=None):
+        """The host events forms (all_matches: the *_matches ones;
+        stream_groups: the *_groups ones, in the form all_matches names):
+        (events u64 ascending, state_out or None).  A host buffer too short
+        for the call's events means one more call with room for all of them,
+        from the same states."""
         arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
                                    else data, dtype=np.uint8)
         offs = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -432,6 +444,10 @@ class HipMatcher:
         nseg = offs.size - 1
         if state is not None and state.shape != (nseg,):
             raise ValueError("state: nseg values")
+        if stream_groups is not None:
+            grp = np.ascontiguousarray(stream_groups, dtype=np.uint32)
+            if grp.shape != (nseg,):
+                raise ValueError("stream_groups: nseg values")
         cap = max(1024, len(arr) // 16)
         while True:
             ev = np.empty(cap, dtype=np.uint64)
@@ -440,7 +456,14 @@ class HipMatcher:
             head = (self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                     offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg)
             tail = (min_len, ev.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), cap, ctypes.byref(total))
-            if state is None:
+            if stream_groups is not None:
+                tail = (grp.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), min_len, int(bool(all_matches))) + tail[1:]
+                if state is None:
+                    rc = self.lib.pm_hip_read_batch_groups(*head, *tail)
+                else:
+                    rc = self.lib.pm_hip_read_flows_groups(*head, st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                           *tail)
+            elif state is None:
                 fn = self.lib.pm_hip_read_batch_matches if all_matches else self.lib.pm_hip_read_batch_events
                 rc = fn(*head, *tail)
             else:
@@ -525,6 +548,75 @@ class HipMatcher:
         nseg = len(offsets) - 1
         st = np.zeros(nseg, dtype=np.uint32) if state is None else np.array(state, dtype=np.uint32, order="C")
         ev, st = self._read_events(data, offsets, st, min_len, all_matches=True)
+        pos, gids = unpack_events(ev)
+        return pos, self._codes[gids], st
+
+    # --- pattern groups: a group mask per pattern and one per stream --------
+    def set_groups(self, masks):
+        """pm_hip_set_groups: masks[k] is the u32 group mask (bit g = member
+        of group g) of the k-th pattern added -- a dictionary's patterns in
+        its own order.  After compile(); a later call replaces the masks
+        (no group scan may be in flight)."""
+        g = np.ascontiguousarray(masks, dtype=np.uint32)
+        if g.ndim != 1:
+            raise ValueError("masks: one u32 per pattern added")
+        rc = self.lib.pm_hip_set_groups(self.obj, g.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), g.size)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def pattern_groups(self, gid):
+        """The group mask of pattern gid (0 out of range or before set_groups)."""
+        return int(self.lib.pm_hip_pattern_groups(self.obj, gid))
+
+    def scan_batch_groups_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_stream_groups_ptr, min_len, all_matches,
+                                 d_events_ptr, cap, d_nevents_ptr, stream_ptr):
+        """pm_hip_scan_batch_groups_device: scan_batch_matches_device with the
+        patterns visible to each stream only (groups & d_stream_groups[j]; a
+        null pointer: every stream on all groups).  all_matches false: the
+        longest visible pattern per position, the answer of a matcher
+        compiled from the visible patterns alone."""
+        rc = self.lib.pm_hip_scan_batch_groups_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n,
+                                                      d_stream_groups_ptr, min_len, int(bool(all_matches)),
+                                                      d_events_ptr, cap, d_nevents_ptr, stream_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def scan_flows_groups_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr,
+                                 d_stream_groups_ptr, min_len, all_matches, d_events_ptr, cap, d_nevents_ptr,
+                                 stream_ptr):
+        """pm_hip_scan_flows_groups_device: scan_flows_matches_device with the
+        list of scan_batch_groups_device; the states do not depend on the
+        masks."""
+        rc = self.lib.pm_hip_scan_flows_groups_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr,
+                                                      d_state_out_ptr, d_stream_groups_ptr, min_len,
+                                                      int(bool(all_matches)), d_events_ptr, cap, d_nevents_ptr,
+                                                      stream_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def read_batch_groups(self, data, offsets, stream_groups, min_len=3, all_matches=True):
+        """pm_hip_read_batch_groups: read_batch_matches with the patterns
+        visible to each stream only (stream_groups: nseg u32 masks):
+        (positions int64, codes), ascending by position, then gid."""
+        ev, _ = self._read_events(data, offsets, None, min_len, all_matches, stream_groups)
+        pos, gids = unpack_events(ev)
+        return pos, self._codes[gids]
+
+    def read_many_groups(self, buffers, stream_groups, min_len=3, all_matches=True):
+        """read_many_matches with a group mask per buffer."""
+        offs = batch_offsets(buffers)
+        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
+        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        pos, codes = self.read_batch_groups(data, offs, stream_groups, min_len, all_matches)
+        return _split_events(pos, codes, offs)
+
+    def read_flows_groups(self, data, offsets, stream_groups, state=None, min_len=3, all_matches=True):
+        """pm_hip_read_flows_groups: read_flows_matches with the patterns
+        visible to each stream only: (positions, codes, state_out)."""
+        nseg = len(offsets) - 1
+        st = np.zeros(nseg, dtype=np.uint32) if state is None else np.array(state, dtype=np.uint32, order="C")
+        ev, st = self._read_events(data, offsets, st, min_len, all_matches, stream_groups)
         pos, gids = unpack_events(ev)
         return pos, self._codes[gids], st
 
