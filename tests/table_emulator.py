@@ -139,15 +139,15 @@ def rt_scan(img, text, stream_start=0, use_filter=True):
     i = np.arange(n, dtype=np.int64)
     avail = i - stream_start + 1
     c0 = text.astype(np.uint32)
-    c1 = np.concatenate([[0], text[:-1]]).astype(np.uint32)
-    c2 = np.concatenate([[0, 0], text[:-2]]).astype(np.uint32)
+    c1 = np.concatenate([[0], text])[:n].astype(np.uint32)  # (text[:-1] would be all of a text of 0 bytes)
+    c2 = np.concatenate([[0, 0], text])[:n].astype(np.uint32)
     v = t12[(c0 << 8) | c1]
     out = v & 0x7FFF
     out[avail == 1] = t12[65536 + c0[avail == 1]]
     key24 = c2 | (c1 << 8) | (c0 << 16)
     cont = ((v & 0x8000) != 0) & (avail >= 3)
     if use_filter:
-        c3 = np.concatenate([[0, 0, 0], text[:-3]]).astype(np.uint32)
+        c3 = np.concatenate([[0, 0, 0], text])[:n].astype(np.uint32)
         cont &= filter_maybe(filt, key24) & filter2_maybe(filt, key24, c3)
     for p in i[cont]:
         e = t3h_lookup(t3h, bits, int(key24[p]))

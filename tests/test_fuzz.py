@@ -5,58 +5,12 @@ byte fans for wide trie nodes, duplicate and rejected lines for the parser,
 every byte value.  CPU: the flattened images through the numpy emulation of
 both kernels.  GPU: all three plugin kinds through read_block and the
 device entry, bit-exact."""
-import os
-
 import numpy as np
 import pytest
 
 import patternmatching_amd as pm
+from fuzz_inputs import fuzz_case, write_dict
 from oracle_lib import Oracle
-
-ALPHABETS = (2, 3, 4, 16, 95, 256)
-
-
-def fuzz_case(seed, stream_bytes):
-    rng = np.random.default_rng(1000 + seed)
-    a = ALPHABETS[seed % len(ALPHABETS)]
-    alphabet = rng.choice(256, size=a, replace=False).astype(np.uint8)
-    n = (30, 300, 3000)[seed % 3]
-    pats = []
-    for _ in range(n):
-        r = rng.random()
-        if pats and r < 0.2:  # a suffix of an earlier pattern (nesting)
-            p = pats[rng.integers(len(pats))]
-            p = p[rng.integers(0, len(p)):]
-        elif pats and r < 0.35:  # an extension (deep chains)
-            p = pats[rng.integers(len(pats))] + bytes(rng.choice(alphabet, 1 + rng.geometric(0.3)))
-        else:
-            p = bytes(rng.choice(alphabet, min(1 + rng.geometric(0.12), 200)))
-        pats.append(p[:200])
-    if a >= 16:  # a wide reversed-trie node: many bytes before one suffix
-        tail = bytes(rng.choice(alphabet, 3))
-        pats += [bytes([c]) + tail for c in alphabet[:40]]
-    lines = [b"|" + b" ".join(b"%02x" % c for c in p) + b"|" for p in pats if p]
-    # the parser's rejections and skips (parser.c:63-99): they only shift line numbers
-    for bad in (b"|41 |", b"|4|", b"|41", b""):
-        lines.insert(int(rng.integers(len(lines) + 1)), bad)
-    # the stream: runs of alphabet bytes and copies of patterns
-    parts, size = [], 0
-    while size < stream_bytes:
-        if rng.random() < 0.5:
-            q = pats[rng.integers(len(pats))]
-        else:
-            q = bytes(rng.choice(alphabet, int(rng.integers(1, 64))))
-        parts.append(q)
-        size += len(q)
-    text = np.frombuffer(b"".join(parts)[:stream_bytes], np.uint8).copy()
-    return b"\n".join(lines) + b"\n", text
-
-
-def write_dict(tmp_path, seed, data):
-    path = os.path.join(str(tmp_path), f"fuzz{seed}.dict")
-    with open(path, "wb") as f:
-        f.write(data)
-    return path
 
 
 @pytest.mark.parametrize("seed", range(12))
