@@ -396,6 +396,85 @@ int pm_hip_read_flows_groups(void* obj, const uint8_t* buf, const int64_t* offse
                              const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
                              size_t* nevents);
 
+/*
+ * Pattern windows: where in its stream a pattern may lie (Snort's and
+ * Suricata's `offset` and `depth`), tested for each match inside the scan,
+ * beside the group test.  Every pattern k, in add order, has two uint32_t:
+ * min_start[k] (`offset`) and max_end[k] (`offset + depth`; 0xFFFFFFFF =
+ * unbounded).  Let E be the number of bytes a position's stream has had
+ * through position i, this one included: in the batched scan E = i - (the
+ * stream's first byte) + 1, in the flow scan E = pos_in[j] + i - offsets[j]
+ * + 1.  A pattern h of L bytes that ends at i PASSES ITS WINDOW iff
+ * E - L >= min_start[h] and E <= max_end[h], compared in 64 bits (the device
+ * compares need = min_start + L and max_end with E saturated to 32 bits,
+ * which is the same test: min_start <= 0x7FFFFFFF, L < 2^31).  A window no
+ * occurrence can satisfy is legal; the pattern is then never reported.
+ * Pattern h is VISIBLE at position i of stream j iff it passes its window
+ * there and is group-visible to j exactly as in "pattern groups"; where
+ * pm_hip_set_groups was never called every pattern is in every group and
+ * d_stream_groups must be NULL (-7 otherwise, as there).
+ *   all != 0: one event i << 24 | h for every visible h of at least min_len
+ *     bytes that ends at i.
+ *   all == 0: at most one event per position, the longest visible pattern of
+ *     at least min_len bytes -- the answer of a matcher that knew only the
+ *     patterns allowed there.  As with groups this is NOT the events list
+ *     filtered: an invisible answer yields to a shorter visible suffix.
+ * With windows a short pattern becomes askable: a 2-byte magic anchored at
+ * (0, 2) is reported at min_len 1 without the flood of its other occurrences.
+ * pm_hip_set_windows(obj, min_start, max_end, n): after compile() (-1
+ * before); -2 for a wrong n, a NULL array or a min_start above 0x7FFFFFFF.
+ * A byte string added twice has the window of the add that wins.  The first
+ * call allocates one table of 16 bytes per pattern (+ 1 entry) on the device,
+ * counted in pm_hip_table_bytes from then on; a later call overwrites it in
+ * place after a device synchronize (no window scan may be in flight).
+ * compile() and the compiled-image cache do not see windows, and an object
+ * that never calls it behaves exactly as before.
+ * pm_hip_pattern_window(obj, gid, &min_start, &max_end): 0; -1 for a gid out
+ * of range or before pm_hip_set_windows (either pointer may be NULL).
+ * pm_hip_scan_batch_windows_device takes the arguments of
+ * pm_hip_scan_batch_groups_device; pm_hip_scan_flows_windows_device those of
+ * pm_hip_scan_flows_groups_device plus d_pos_in, a DEVICE pointer to nseg
+ * uint64_t, 8-byte aligned, the bytes each flow had before this call (NULL =
+ * every flow at byte 0), and d_pos_out (NULL = not wanted; -2 if it equals
+ * d_pos_in), which receives d_pos_in[j] + offsets[j+1] - offsets[j]; an empty
+ * stream copies its position, also in the n == 0 copy pass.  Flow states do
+ * not depend on windows, masks or positions: d_state_out is the dense flow
+ * call's.  Every other rule is the group siblings'; one new code, -8:
+ * pm_hip_set_windows was not called (nothing is launched or written).  The
+ * calls allocate nothing and may be captured.
+ * The host forms work like pm_hip_read_*_groups; the flow form's pos is a
+ * HOST array of nseg uint64_t, read and overwritten like state (NULL = all
+ * zero, nothing returned).
+ * Measured (64 MiB, all form, every stream on all groups, fresh flows;
+ * profiles/windows/): with every window unbounded the calls take, over the
+ * group calls of the same run, 1.005-1.023x (batched) and 1.030-1.037x (flow)
+ * on random ASCII, 1.042-1.048x and 1.121-1.142x on the lines stream, where
+ * every position walks a deep chain and each member costs one more 16-byte
+ * table entry; with a third of the patterns limited to the first 256 bytes
+ * 0.998-1.023x / 1.026-1.035x on ASCII and 1.032-1.040x / 1.094-1.126x on
+ * lines.  At min_len 1 with every pattern of at most 2 bytes anchored at
+ * (0, len) a 64 MiB call takes 521-947 us batched and 452-605 us as flows on
+ * ASCII (the dense-id call: 485-817 and 362-438 us), 6.7-9.2 ms and 2.8-3.6
+ * ms on lines (4.2-5.8 and 1.2-1.3 ms).
+ */
+int pm_hip_set_windows(void* obj, const uint32_t* min_start, const uint32_t* max_end, size_t n);
+int pm_hip_pattern_window(void* obj, uint32_t gid, uint32_t* min_start, uint32_t* max_end);
+int pm_hip_scan_batch_windows_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                     int64_t n, const uint32_t* d_stream_groups, uint32_t min_len, int all,
+                                     uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                     void* hip_stream);
+int pm_hip_scan_flows_windows_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                     int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out,
+                                     const uint32_t* d_stream_groups, uint32_t min_len, int all, uint64_t* d_events,
+                                     uint64_t cap, unsigned long long* d_nevents, void* hip_stream,
+                                     const uint64_t* d_pos_in, uint64_t* d_pos_out);
+int pm_hip_read_batch_windows(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg,
+                              const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
+                              size_t* nevents);
+int pm_hip_read_flows_windows(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                              uint64_t* pos, const uint32_t* stream_groups, uint32_t min_len, int all,
+                              uint64_t* events, size_t cap, size_t* nevents);
+
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,
  * PatternsTree.c:485-494): per position, equal -> success; d_algo's pattern
@@ -636,6 +715,26 @@ int pm_flat_group_tables(void* handle, const uint32_t* groups_by_index, size_t n
 int pm_flat_expand_groups(void* handle, const uint32_t* gids, size_t n, const int64_t* offsets, size_t nseg,
                           const uint32_t* stream_groups, const uint32_t* groups_by_index, uint32_t min_len, int all,
                           uint64_t* events, size_t cap, size_t* nevents);
+/* Pattern windows on the host (above).  pm_flat_window_tables: from
+ * min_start and max_end per pattern in add order (n = the patterns added),
+ * exactly the array pm_hip_set_windows uploads: 4 u32 per gid, n + 1 gids,
+ *   win[4g] = need = min_start + len      win[4g+1] = max_end
+ *   win[4g+2] = the minimum of need, win[4g+3] = the maximum of max_end over
+ *   g's suffix chain;
+ * entry 0 is { 0xFFFFFFFF, 0, 0xFFFFFFFF, 0 } (never passes; neutral for the
+ * two folds).  Returns 0; -2 for a wrong n, a NULL pointer or a min_start
+ * above 0x7FFFFFFF (nothing written).
+ * pm_flat_expand_windows: the window list of n dense gids, for either image
+ * kind and either form; pos_in NULL = every stream at byte 0; stream_groups
+ * and groups_by_index may be NULL (no group tables: every pattern in every
+ * group; stream_groups without groups_by_index is -2).  Output rules and
+ * return codes as pm_flat_expand_groups. */
+int pm_flat_window_tables(void* handle, const uint32_t* min_start_by_index, const uint32_t* max_end_by_index, size_t n,
+                          uint32_t* win_out);
+int pm_flat_expand_windows(void* handle, const uint32_t* gids, size_t n, const int64_t* offsets, size_t nseg,
+                           const uint64_t* pos_in, const uint32_t* stream_groups, const uint32_t* groups_by_index,
+                           const uint32_t* min_start_by_index, const uint32_t* max_end_by_index, uint32_t min_len,
+                           int all, uint64_t* events, size_t cap, size_t* nevents);
 void pm_flat_free(void* handle);
 
 #ifdef __cplusplus

@@ -23,7 +23,10 @@ interface:
                     FlowTable.scan_matches), and their group forms: a group
                     mask per pattern (HipMatcher.set_groups) and per stream
                     (HipMatcher.read_*_groups / scan_*_groups_device,
-                    FlowTable.scan_groups)
+                    FlowTable.scan_groups), and their window forms: where in
+                    its stream a pattern may lie, Snort's offset and depth
+                    (HipMatcher.set_windows, read_*_windows /
+                    scan_*_windows_device, FlowTable.scan_windows)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401

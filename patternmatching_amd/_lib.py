@@ -139,6 +139,21 @@ SIGNATURES = {
                                                 c_u32p, ctypes.c_uint32, ctypes.c_int,
                                                 ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
                                                 ctypes.POINTER(ctypes.c_size_t)]),
+    "pm_hip_set_windows": (ctypes.c_int, [c_vp, c_u32p, c_u32p, ctypes.c_size_t]),
+    "pm_hip_pattern_window": (ctypes.c_int, [c_vp, ctypes.c_uint32, c_u32p, c_u32p]),
+    "pm_hip_scan_batch_windows_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp,
+                                                        ctypes.c_uint32, ctypes.c_int, c_vp, ctypes.c_uint64, c_vp,
+                                                        c_vp]),
+    "pm_hip_scan_flows_windows_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp,
+                                                        c_vp, ctypes.c_uint32, ctypes.c_int, c_vp, ctypes.c_uint64,
+                                                        c_vp, c_vp, c_vp, c_vp]),
+    "pm_hip_read_batch_windows": (ctypes.c_int, [c_vp, c_u8p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, c_u32p,
+                                                 ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
+                                                 ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "pm_hip_read_flows_windows": (ctypes.c_int, [c_vp, c_u8p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, c_u32p,
+                                                 ctypes.POINTER(ctypes.c_uint64), c_u32p, ctypes.c_uint32,
+                                                 ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+                                                 ctypes.POINTER(ctypes.c_size_t)]),
     "pm_hip_score_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp]),
     "pm_hip_parent_gid": (ctypes.c_uint32, [c_vp, ctypes.c_uint32]),
     "pm_hip_set_image_cache": (None, [c_vp, ctypes.c_char_p]),
@@ -196,6 +211,12 @@ SIGNATURES = {
                                              ctypes.c_size_t, c_u32p, c_u32p, ctypes.c_uint32, ctypes.c_int,
                                              ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
                                              ctypes.POINTER(ctypes.c_size_t)]),
+    "pm_flat_window_tables": (ctypes.c_int, [c_vp, c_u32p, c_u32p, ctypes.c_size_t, c_u32p]),
+    "pm_flat_expand_windows": (ctypes.c_int, [c_vp, c_u32p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64),
+                                              ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64), c_u32p, c_u32p,
+                                              c_u32p, c_u32p, ctypes.c_uint32, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+                                              ctypes.POINTER(ctypes.c_size_t)]),
 }
 
 _lib = None

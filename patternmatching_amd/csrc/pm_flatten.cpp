@@ -476,6 +476,62 @@ void pm_expand_groups(const PmGidMap& g, const PmParents& par, const PmGroupTabl
     *nevents = total;
 }
 
+PmWindowTables pm_window_tables(const PmGidMap& g, const PmParents& par, const uint32_t* min_start_by_index,
+                                const uint32_t* max_end_by_index) {
+    const size_t G = g.index_of_gid.size();
+    PmWindowTables t;
+    t.win.assign(4 * G, 0);
+    if (G) t.win[0] = t.win[2] = 0xFFFFFFFFu;
+    for (size_t q = 1; q < G; ++q) {
+        const uint64_t need = (uint64_t)min_start_by_index[g.index_of_gid[q]] + g.len[q];
+        t.win[4 * q] = need > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)need;
+        t.win[4 * q + 1] = max_end_by_index[g.index_of_gid[q]];
+    }
+    // a parent is one level shallower than its child: by depth, parents first
+    std::vector<uint32_t> order(G);
+    for (size_t q = 0; q < G; ++q) order[q] = (uint32_t)q;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return par.depth[a] < par.depth[b]; });
+    for (uint32_t q : order)
+        if (q) {
+            const uint32_t p = par.parent[q];
+            t.win[4 * q + 2] = std::min(t.win[4 * q], t.win[4 * p + 2]);
+            t.win[4 * q + 3] = std::max(t.win[4 * q + 1], t.win[4 * p + 3]);
+        }
+    return t;
+}
+
+void pm_expand_windows(const PmGidMap& g, const PmParents& par, const PmGroupTables* gt, const PmWindowTables& wt,
+                       const uint32_t* gids, size_t n, const int64_t* offsets, size_t nseg, const uint64_t* pos_in,
+                       const uint32_t* stream_groups, uint32_t min_len, bool all, uint64_t* events, size_t cap,
+                       size_t* nevents) {
+    size_t total = 0, j = 0;
+    std::vector<uint64_t> one;
+    for (size_t k = 0; k < n && nseg; ++k) {
+        // the stream holding k: the last one that begins at or before k (offsets ascend), below nseg
+        while (j + 1 < nseg && offsets[j + 1] <= (int64_t)k) ++j;
+        uint32_t h = gids[k];
+        if (h == 0 || h >= par.parent.size()) continue;
+        const uint32_t sm = gt && stream_groups ? stream_groups[j] : 0xFFFFFFFFu;
+        const uint64_t E = (pos_in ? pos_in[j] : 0) + (uint64_t)k - (uint64_t)offsets[j] + 1;
+        one.clear();
+        for (uint32_t d = par.depth[h]; d > 0 && h != 0 && g.len[h] >= min_len; --d, h = par.parent[h]) {
+            const uint32_t* w = &wt.win[4 * (size_t)h];
+            if (gt && !(gt->reach[h] & sm)) break;
+            if (E < w[2] || (w[3] != 0xFFFFFFFFu && E > w[3])) break;
+            if (gt && !(gt->gmask[h] & sm)) continue;
+            if (E < w[0] || (w[1] != 0xFFFFFFFFu && E > w[1])) continue;
+            one.push_back((uint64_t)k << 24 | h);
+            if (!all) break;
+        }
+        std::sort(one.begin(), one.end());
+        for (const uint64_t e : one) {
+            if (total < cap) events[total] = e;
+            ++total;
+        }
+    }
+    *nevents = total;
+}
+
 // The sparse form (pm_flatten.h).  order: states by depth, so a state's
 // failure (shallower) is decided before it.  The fallback of v is fail[v]
 // when that keeps a row, else fail[v]'s own fallback; then delta(v, c) =

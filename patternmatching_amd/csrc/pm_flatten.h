@@ -177,6 +177,32 @@ void pm_expand_groups(const PmGidMap& g, const PmParents& par, const PmGroupTabl
                       const int64_t* offsets, size_t nseg, const uint32_t* stream_groups, uint32_t min_len, bool all,
                       uint64_t* events, size_t cap, size_t* nevents);
 
+// Pattern windows (pm_hip.h, "pattern windows") in gid space, from two u32
+// values per pattern in add order (min_start, and max_end with 0xFFFFFFFF =
+// unbounded): win[4 g ..] = { need, max_end, chain_need, chain_max } with
+// need = min_start + len (saturated at 0xFFFFFFFF), chain_need the minimum of
+// need and chain_max the maximum of max_end over g's suffix chain.  A pattern
+// whose stream has had E bytes through the position it ends at passes its
+// window iff need <= E <= max_end; nothing on its chain can iff E <
+// chain_need or E > chain_max.  Entry 0 is { ~0, 0, ~0, 0 }: it never
+// passes and is the neutral element of both folds.  Duplicates as in
+// pm_group_tables.
+struct PmWindowTables {
+    std::vector<uint32_t> win;  // 4 per gid
+};
+PmWindowTables pm_window_tables(const PmGidMap& g, const PmParents& par, const uint32_t* min_start_by_index,
+                                const uint32_t* max_end_by_index);
+
+// The window match list of n dense gids on the host (the contract of the
+// window kernels): pm_expand_groups where a member h must also pass its
+// window, with E = pos_in[j] + k - offsets[j] + 1 in 64 bits (pos_in null:
+// all 0).  gt null: every pattern is in every group (stream_groups is then
+// ignored).
+void pm_expand_windows(const PmGidMap& g, const PmParents& par, const PmGroupTables* gt, const PmWindowTables& wt,
+                       const uint32_t* gids, size_t n, const int64_t* offsets, size_t nseg, const uint64_t* pos_in,
+                       const uint32_t* stream_groups, uint32_t min_len, bool all, uint64_t* events, size_t cap,
+                       size_t* nevents);
+
 // The sparse form with 8-B record units (a device layout, built from the
 // 16-B form at compile time; not cached): rows [0, F) as before, then the
 // records in the same order, each at a unit offset u with state id F + u:

@@ -193,6 +193,34 @@ hipError_t pm_launch_dfa_flows_groups(const uint8_t* text, const int64_t* offset
                                       const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
                                       const MatchDev& mx, const GroupDev& gr, bool all, const DfaDev& t,
                                       uint32_t states, int64_t force_seg, int num_cu, hipStream_t s);
+// What the window forms add (pm_hip.h, "pattern windows"): win[g], one 16-B
+// entry per gid (n_patterns + 1 of them; pm_window_tables):
+//   .x need = min_start + len     .y max_end
+//   .z the minimum of need over g's suffix chain   .w the maximum of max_end over it
+// With E the bytes g's stream has had through a position (saturated to u32,
+// which changes no comparison: 0xFFFFFFFF is "unbounded"), g passes its
+// window iff x <= E <= y, and nothing on its chain can iff E < z or E > w.
+// Entry 0 is {~0, 0, ~0, 0}: never passes, the neutral element of z and w.
+// pos_in / pos_out (the flow form only): the bytes each flow had before the
+// call and has after it, nseg values; nullptr = all 0 / not wanted.
+struct WinDev {
+    const uint4* win;
+    const uint64_t* pos_in;
+    uint64_t* pos_out;
+};
+// pm_launch_rt_batch_groups / pm_launch_dfa_flows_groups with a pattern
+// visible only where it also passes its window (rt_batch_windows_kernel,
+// dfa_flow_windows_kernel).  gr.gmask == nullptr (the object has no group
+// tables): every pattern is in every group and gr.stream_groups is nullptr.
+// The flow form with n == 0 copies the empty streams' states and positions.
+hipError_t pm_launch_rt_batch_windows(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                      const EvDev& ev, const MatchDev& mx, const GroupDev& gr, const WinDev& wn,
+                                      bool all, const RtDev& t, int num_cu, hipStream_t s);
+hipError_t pm_launch_dfa_flows_windows(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                       const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
+                                       const MatchDev& mx, const GroupDev& gr, const WinDev& wn, bool all,
+                                       const DfaDev& t, uint32_t states, int64_t force_seg, int num_cu,
+                                       hipStream_t s);
 // The sparse kernel (PmSparseKernel) a launch of this width runs, 0 when
 // it runs dense rows: the forced DfaDev::sparse_kernel where the object
 // and width allow it, else the product choice.

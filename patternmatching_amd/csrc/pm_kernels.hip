@@ -2637,6 +2637,320 @@ __global__ __launch_bounds__(DFA_THREADS) void dfa_flow_groups_kernel(
             if (offs[j + 1] <= offs[j]) state_out[j] = load_state(j);
 }
 
+// ---- pattern windows: where in its stream a pattern may lie ---------------------
+// The window forms of the two group kernels (pm_hip.h, "pattern windows"):
+// pattern h is visible at position i of stream j iff it is group-visible to j
+// as above AND passes its window there: with E the bytes the stream has had
+// through i, need[h] <= E <= max_end[h] (WinDev; need = min_start + len).
+// Kernels of their own once more, the group kernels' text with the window
+// test added to the member filter; pending and emit are kept apart exactly as
+// there.  The pruning idea of reach carries over: a chain is dead at E where
+// E is below every member's need or above every member's max_end (the entry's
+// .z and .w), so a window that shuts the whole chain costs one 16-B load and
+// no walk.  Unlike reach the test depends on the position, and it is a
+// necessary condition only: a chain that is not dead may still emit nothing.
+// E is saturated to 32 bits: need <= 0xFFFFFFFF and max_end == 0xFFFFFFFF is
+// "unbounded", so no comparison changes.  The batched kernel's lane holds its
+// stream's clamped first byte (start) and needs no stream index for E; it
+// searches for j only where stream masks are given, as before.  The flow
+// kernel's lanes load pos_in[j] where they load the state and the mask, keep
+// pb = pos_in[j] - offs[j] (E = pb + i + 1) for the step they began with
+// (pb0, like sm0), and write pos_out[j] = pb + offs[j + 1] where they write
+// state_out[j]; the last pass copies the empty streams' positions too.
+// The group tables are read only where the object has them (gr.gmask, a
+// uniform branch); without them gr.stream_groups is null.
+__device__ __forceinline__ uint32_t win_sat(uint64_t e) { return e > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)e; }
+// win_sat(E + q) from e = win_sat(E), q < 16
+__device__ __forceinline__ uint32_t win_add(uint32_t e, uint32_t q) { return e + q < e ? 0xFFFFFFFFu : e + q; }
+
+template <bool SMALL, bool ALL>
+__global__ __launch_bounds__(RT_THREADS) void rt_batch_windows_kernel(const uint8_t* __restrict__ text,
+                                                                      const int64_t* __restrict__ offs, int64_t nseg,
+                                                                      int64_t n, EvDev ev, MatchDev mx, GroupDev gr,
+                                                                      WinDev wn, RtDev t) {
+    constexpr int kT12Words = SMALL ? 0 : RT_T2_U16 / 2;
+    constexpr int kStageWords = (RT_THREADS / 64) * RT_EV_STAGE * 2;
+    __shared__ __attribute__((aligned(16))) uint32_t s_lds[kT12Words + kStageWords + RT_BATCH_TILE / 32];
+    uint32_t* const s_mask = s_lds + kT12Words + kStageWords;
+    const uint16_t* s_t = t.t12;
+    const int tid = threadIdx.x;
+    EvWave<RT_EV_STAGE> stage{reinterpret_cast<uint64_t*>(s_lds + kT12Words) + (tid >> 6) * RT_EV_STAGE, 0u};
+    if (!SMALL) {
+        const uint4* src = reinterpret_cast<const uint4*>(t.t12);
+        uint4* dst = reinterpret_cast<uint4*>(s_lds);
+        for (int k = tid; k < RT_T2_U16 * 2 / 16; k += RT_THREADS) dst[k] = src[k];
+        __syncthreads();
+        s_t = reinterpret_cast<const uint16_t*>(s_lds);
+    }
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t T0 = ntiles * (int64_t)blockIdx.x / (int64_t)gridDim.x;
+    const int64_t T1 = ntiles * ((int64_t)blockIdx.x + 1) / (int64_t)gridDim.x;
+    const int64_t noffs = nseg + 1;
+    const bool grp = gr.gmask != nullptr;  // uniform: the object has group tables
+    int64_t a = batch_seek(offs, 0, noffs, T0 * RT_BATCH_TILE + 1);
+    for (int64_t T = T0; T < T1; ++T) {
+        const int64_t base = T * RT_BATCH_TILE;
+        const int64_t end = base + RT_BATCH_TILE < n ? base + RT_BATCH_TILE : n;
+        a = batch_seek(offs, a, noffs, base + 1);
+        const int64_t b = batch_seek(offs, a, noffs, end);
+        int64_t start = a > 0 ? (int64_t)rfl64((uint64_t)offs[a - 1]) : 0;
+        bool first = true;  // no stream begins in (base, i]: the lane's stream is a - 1, the tile's first
+        if (b > a) {  // workgroup-uniform
+            __syncthreads();
+            if (tid < RT_BATCH_TILE / 32) s_mask[tid] = 0u;
+            __syncthreads();
+            for (int64_t j = a + tid; j < b; j += RT_THREADS) {
+                const int64_t rel = offs[j] - base;
+                if (rel > 0 && rel < RT_BATCH_TILE) atomicOr(&s_mask[rel >> 5], 1u << (rel & 31));
+            }
+            __syncthreads();
+            int w = tid >> 5;
+            uint32_t m = s_mask[w] & (0xFFFFFFFFu >> (31 - (tid & 31)));
+            while (!m && w > 0) m = s_mask[--w];
+            if (m) {
+                start = base + w * 32 + 31 - __clz(m);
+                first = false;
+            }
+        }
+        const int64_t i = base + tid;
+        uint32_t v = 0;
+        if (i < n) {
+            start = start < 0 ? 0 : start > i ? i : start;
+            v = rt_one(text, s_t, t, i, start);
+        }
+        // all 64 lanes of every wave are here (a lane past n holds v = 0)
+        uint32_t h = 0u;  // the lane's pending chain member, 0 = done
+        bool emit = false;  // h is visible at i
+        uint32_t sm = 0xFFFFFFFFu;
+        // the bytes the lane's stream has had through i (a lane past n: unused)
+        const uint32_t E = win_sat((uint64_t)(i - start) + 1u);
+        const bool k0 = ev_keep(v, ev);
+        if (__ballot(k0)) {  // wave-uniform: one wave in 20 on random ASCII
+            // the loads in flight at once: the mask of the tile's first stream (a wave-uniform
+            // address) and the head's table entries
+            if (grp && gr.stream_groups) sm = gr.stream_groups[a < 1 ? 0 : a > nseg ? nseg - 1 : a - 1];
+            if (k0) {
+                const uint4 w = wn.win[v];
+                uint32_t rc = 0xFFFFFFFFu, gm = 0xFFFFFFFFu;
+                if (grp) {
+                    rc = gr.reach[v];
+                    gm = gr.gmask[v];
+                    if (gr.stream_groups && !first) {
+                        // the stream holding i: the first offset > i, minus one; offs[a - 1] <= base, offs[b] >= end
+                        int64_t j = flow_seek(offs, a, b + 1 < noffs ? b + 1 : noffs, i + 1) - 1;
+                        j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+                        sm = gr.stream_groups[j];
+                    }
+                }
+                if ((rc & sm) && E >= w.z && E <= w.w) {
+                    h = v;
+                    emit = (gm & sm) != 0u && E >= w.x && E <= w.y;
+                }
+            }
+        }
+        if (__ballot(h != 0u)) {
+            for (uint32_t d = 0;;) {  // wave-uniform; round 0 is the heads'
+                const uint64_t em = __ballot(emit);
+                if (em) {
+                    const EvSlot slot = ev_reserve(stage, (uint32_t)__popcll(em), ev);
+                    if (emit) ev_put(stage, slot, wave_prefix(em), (uint64_t)i << PM_EV_GID_BITS | h, ev);
+                }
+                if (!ALL && emit) h = 0u;
+                if (++d >= mx.max_depth) break;
+                emit = false;
+                if (h) {
+                    const uint32_t p = mx.parent[h];
+                    h = 0u;
+                    if (ev_keep(p, ev)) {  // most chains end here (gid 0), with no table load
+                        const uint4 w = wn.win[p];
+                        uint32_t rc = 0xFFFFFFFFu, gm = 0xFFFFFFFFu;
+                        if (grp) {
+                            rc = gr.reach[p];
+                            gm = gr.gmask[p];
+                        }
+                        if ((rc & sm) && E >= w.z && E <= w.w) {
+                            h = p;
+                            emit = (gm & sm) != 0u && E >= w.x && E <= w.y;
+                        }
+                    }
+                }
+                if (!__ballot(h != 0u)) break;
+            }
+        }
+        a = b;
+    }
+    ev_flush(stage, ev);
+}
+
+template <bool CODED, bool ALL>
+__global__ __launch_bounds__(DFA_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void dfa_flow_windows_kernel(
+    const uint8_t* __restrict__ text, const int64_t* __restrict__ offs, int64_t nseg, int64_t n,
+    const uint32_t* __restrict__ state_in, uint32_t* __restrict__ state_out, EvDev ev, MatchDev mx, GroupDev gr,
+    WinDev wn, const uint32_t* __restrict__ nxt, const uint32_t* __restrict__ outt, uint32_t states, int64_t warm,
+    int64_t seg_len, const uint32_t* __restrict__ gram3) {
+    __shared__ uint64_t s_stage[(DFA_THREADS / 64) * DFA_EV_STAGE];
+    EvWave<DFA_EV_STAGE> stage{s_stage + (threadIdx.x >> 6) * DFA_EV_STAGE, 0u};
+    const int64_t nlane = (n + seg_len - 1) / seg_len;
+    const int64_t stride = (int64_t)gridDim.x * DFA_THREADS;
+    const int64_t gtid = (int64_t)blockIdx.x * DFA_THREADS + threadIdx.x;
+    const int64_t noffs = nseg + 1;
+    const bool grp = gr.gmask != nullptr;  // uniform: the object has group tables
+    auto load_state = [&](int64_t j) -> uint32_t {  // j in [0, nseg)
+        const uint32_t s = state_in ? state_in[j] : 0u;
+        return s < states ? s : 0u;
+    };
+    auto load_mask = [&](int64_t j) -> uint32_t {  // j in [0, nseg)
+        return grp && gr.stream_groups ? gr.stream_groups[j] : 0xFFFFFFFFu;
+    };
+    auto load_pos = [&](int64_t j) -> uint64_t {  // j in [0, nseg)
+        return wn.pos_in ? wn.pos_in[j] : 0ull;
+    };
+    for (int64_t sg0 = gtid - (threadIdx.x & 63); sg0 < nlane; sg0 += stride) {  // wave-uniform
+        const int64_t sg = sg0 + (threadIdx.x & 63);
+        int64_t i = 0, hi = 0, end = 0, j = 0;  // a lane without a segment: no step
+        uint32_t s = 0, sm = 0;
+        uint64_t pb = 0;  // pos_in[j] - offs[j]: position p of stream j is its byte pb + p (from 0)
+        if (sg < nlane) {
+            const int64_t lo = sg * seg_len;
+            hi = lo + seg_len < n ? lo + seg_len : n;
+            // the stream holding lo: the first offset > lo, minus one
+            j = flow_seek(offs, 0, noffs, lo + 1) - 1;
+            j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+            int64_t start = offs[j];
+            pb = load_pos(j) - (uint64_t)start;
+            start = start < 0 ? 0 : start > lo ? lo : start;
+            end = offs[j + 1];
+            sm = load_mask(j);
+            int64_t wlo = lo - warm;
+            if (wlo < start) wlo = start;
+            int64_t w = wlo;
+            if (gram3) w = dfa_sync_lo(text, lo, wlo, gram3);  // in [wlo, lo]: never before start
+            s = (w == wlo && wlo == start) ? load_state(j) : 0u;
+            for (int64_t k = w; k < lo; ++k) {
+                const uint32_t v = nxt[(size_t)s * 256 + text[k]];
+                s = CODED ? v & DFA_STATE_MASK : v;
+            }
+            i = lo;
+        }
+        while (__any(i < hi)) {  // wave-uniform: one step of every lane that has positions left
+            const int64_t p0 = i;
+            const uint32_t sm0 = sm;  // the mask of the stream this step's positions lie in
+            const uint32_t e0 = win_sat(pb + (uint64_t)p0 + 1u);  // the bytes that stream has had through p0
+            uint32_t r[16];
+            uint32_t keep = 0;  // bit q: position p0 + q has a pending chain member r[q]
+            if (i < hi) {
+                if ((i & 15) == 0 && i + 16 <= hi && i + 16 <= end) {
+                    const uint4 tw = *reinterpret_cast<const uint4*>(text + i);
+                    const uint32_t W[4] = {tw.x, tw.y, tw.z, tw.w};
+                    uint32_t st[16];
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const uint32_t v = nxt[(size_t)s * 256 + ((W[q >> 2] >> (8 * (q & 3))) & 0xFFu)];
+                        s = CODED ? v & DFA_STATE_MASK : v;
+                        r[q] = CODED ? v >> 20 : 0u;
+                        st[q] = s;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        if (CODED) r[q] = r[q] == DFA_ESC ? outt[st[q]] : r[q];
+                        else r[q] = outt[st[q]];
+                        keep |= (uint32_t)ev_keep(r[q], ev) << q;
+                    }
+                    i += 16;
+                } else {
+                    const uint32_t v = nxt[(size_t)s * 256 + text[i]];
+                    s = CODED ? v & DFA_STATE_MASK : v;
+                    uint32_t id = CODED ? v >> 20 : outt[s];
+                    if (CODED && id == DFA_ESC) id = outt[s];
+                    r[0] = id;
+                    keep = (uint32_t)ev_keep(id, ev);
+                    ++i;
+                }
+                if (i == end) {  // position end - 1 was stream j's last byte
+                    if (state_out) state_out[j] = s;
+                    if (wn.pos_out) wn.pos_out[j] = pb + (uint64_t)end;
+                    if (i < hi) {
+                        // the next stream that is not empty: the first offset > i, minus one
+                        j = flow_seek(offs, j + 2 < noffs ? j + 2 : noffs, noffs, i + 1) - 1;
+                        j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+                        pb = load_pos(j) - (uint64_t)offs[j];
+                        end = offs[j + 1];
+                        s = load_state(j);
+                        sm = load_mask(j);
+                    }
+                }
+            }
+            uint32_t emit = 0;  // bit q: r[q] is visible at p0 + q
+            // the heads that passed ev_keep: the window entry, and with group tables reach and
+            // the head's own mask.  Four positions' loads are asked for together (a slot without
+            // a head reads entry 0), so a step waits for memory once per quarter, not per head.
+#pragma unroll
+            for (int q0 = 0; q0 < 16; q0 += 4)
+                if ((keep >> q0) & 0xFu) {
+                    uint4 w[4];
+                    uint32_t rc[4], gm[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const uint32_t g = (keep >> (q0 + q)) & 1u ? r[q0 + q] : 0u;
+                        w[q] = wn.win[g];
+                        rc[q] = grp ? gr.reach[g] : 0xFFFFFFFFu;
+                        gm[q] = grp ? gr.gmask[g] : 0xFFFFFFFFu;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if ((keep >> (q0 + q)) & 1u) {
+                            const uint32_t E = win_add(e0, (uint32_t)(q0 + q));
+                            if (!(rc[q] & sm0) || E < w[q].z || E > w[q].w) keep &= ~(1u << (q0 + q));
+                            else if ((gm[q] & sm0) && E >= w[q].x && E <= w[q].y) emit |= 1u << (q0 + q);
+                        }
+                }
+            // all 64 lanes are here
+            if (__any(keep != 0u)) {
+                for (uint32_t d = 0;;) {  // wave-uniform; round 0 is the heads'
+                    if (__any(emit != 0u)) {
+                        const uint32_t c = __popc(emit);
+                        const uint32_t incl = wave_scan_incl(c);
+                        const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
+                        const EvSlot slot = ev_reserve(stage, total, ev);
+                        uint32_t k = incl - c;
+#pragma unroll
+                        for (int q = 0; q < 16; ++q)
+                            if ((emit >> q) & 1u)
+                                ev_put(stage, slot, k++, (uint64_t)(p0 + q) << PM_EV_GID_BITS | r[q], ev);
+                    }
+                    if (!ALL) keep &= ~emit;
+                    if (++d >= mx.max_depth) break;
+                    emit = 0;
+                    // r[q] = parent[r[q]] in place; a member that fails the filter ends its chain
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if ((keep >> q) & 1u) {
+                            const uint32_t h = mx.parent[r[q]];
+                            const uint4 w = wn.win[h];
+                            const uint32_t rc = grp ? gr.reach[h] : 0xFFFFFFFFu, gm = grp ? gr.gmask[h] : 0xFFFFFFFFu;
+                            const uint32_t E = win_add(e0, (uint32_t)q);
+                            if (ev_keep(h, ev) && (rc & sm0) && E >= w.z && E <= w.w) {
+                                r[q] = h;
+                                if ((gm & sm0) && E >= w.x && E <= w.y) emit |= 1u << q;
+                            } else {
+                                keep &= ~(1u << q);
+                            }
+                        }
+                    if (!__any(keep != 0u)) break;
+                }
+            }
+        }
+    }
+    ev_flush(stage, ev);
+    // empty streams keep their state (as used: an invalid one is the root) and their position
+    if (state_out || wn.pos_out)
+        for (int64_t j = gtid; j < nseg; j += stride)
+            if (offs[j + 1] <= offs[j]) {
+                if (state_out) state_out[j] = load_state(j);
+                if (wn.pos_out) wn.pos_out[j] = load_pos(j);
+            }
+}
+
 // The sparse (default-transition) form, pm_flatten.h: rows only for the
 // states whose row differs from their fallback's in more than PM_SDFA_K
 // bytes, 16-B records for the rest (8-B units in pm_pack_sparse8's
@@ -3927,6 +4241,26 @@ hipError_t pm_launch_rt_batch_groups(const uint8_t* text, const int64_t* offsets
     return hipGetLastError();
 }
 
+// Its window form (rt_batch_windows_kernel): the same launch.  The group
+// tables come together or not at all, and stream masks only with them.
+hipError_t pm_launch_rt_batch_windows(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                      const EvDev& ev, const MatchDev& mx, const GroupDev& gr, const WinDev& wn,
+                                      bool all, const RtDev& t, int num_cu, hipStream_t s) {
+    if (n <= 0 || nseg <= 0) return hipSuccess;
+    if (!text || !offsets || num_cu <= 0) return hipErrorInvalidValue;
+    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent || !wn.win ||
+        !gr.gmask != !gr.reach || (!gr.gmask && gr.stream_groups))
+        return hipErrorInvalidValue;
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
+    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
+    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    auto* const k = small ? (all ? rt_batch_windows_kernel<true, true> : rt_batch_windows_kernel<true, false>)
+                          : (all ? rt_batch_windows_kernel<false, true> : rt_batch_windows_kernel<false, false>);
+    hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, ev, mx, gr, wn, t);
+    return hipGetLastError();
+}
+
 hipError_t pm_launch_rt_serve(PmServeReq* req, uint64_t* fwd, uint32_t* done, int blocks, uint64_t seen,
                               uint64_t gen, int64_t idle_ticks, const RtDev& t, hipStream_t s) {
     if (blocks <= 0) return hipErrorInvalidValue;
@@ -4220,6 +4554,30 @@ hipError_t pm_launch_dfa_flows_groups(const uint8_t* text, const int64_t* offset
                             : (all ? dfa_flow_groups_kernel<false, true> : dfa_flow_groups_kernel<false, false>);
     hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev, mx, gr, t.next, t.out, states,
                        t.warm, seg, g3);
+    return hipGetLastError();
+}
+
+// Its window form (dfa_flow_windows_kernel): the same launch; with n == 0 the
+// copy pass runs for the positions too.
+hipError_t pm_launch_dfa_flows_windows(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                       const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
+                                       const MatchDev& mx, const GroupDev& gr, const WinDev& wn, bool all,
+                                       const DfaDev& t, uint32_t states, int64_t force_seg, int num_cu,
+                                       hipStream_t s) {
+    if (nseg <= 0 || n < 0 || (n == 0 && !state_out && !wn.pos_out)) return hipSuccess;
+    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
+    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent || !wn.win ||
+        !gr.gmask != !gr.reach || (!gr.gmask && gr.stream_groups))
+        return hipErrorInvalidValue;
+    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
+    int64_t seg, blocks;
+    if (!flow_shape(nseg, n, 16, force_seg, num_cu, seg, blocks)) return hipErrorInvalidValue;
+    const dim3 g((unsigned)blocks), b(DFA_THREADS);
+    const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
+    auto* const k = t.coded ? (all ? dfa_flow_windows_kernel<true, true> : dfa_flow_windows_kernel<true, false>)
+                            : (all ? dfa_flow_windows_kernel<false, true> : dfa_flow_windows_kernel<false, false>);
+    hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev, mx, gr, wn, t.next, t.out,
+                       states, t.warm, seg, g3);
     return hipGetLastError();
 }
 

@@ -261,6 +261,10 @@ struct BatchStage {
     // the group calls' stream masks (pm_hip_read_*_groups), cap_grp of them
     uint32_t* d_grp = nullptr;
     size_t cap_grp = 0;
+    // the flow window call's byte counts in and out (pm_hip_read_flows_windows), cap_pos of each
+    uint64_t* d_pos_in = nullptr;
+    uint64_t* d_pos_out = nullptr;
+    size_t cap_pos = 0;
     hipStream_t s = nullptr;
 };
 struct PmHip {
@@ -286,6 +290,9 @@ struct PmHip {
     std::vector<uint32_t> gmask;  // host copy of d_gmask (pm_hip_pattern_groups)
     uint32_t* d_gmask = nullptr;  // in allocs
     uint32_t* d_reach = nullptr;
+    // pattern windows (pm_hip_set_windows): nothing before its first call
+    std::vector<uint32_t> win;  // host copy of d_win, 4 per gid (pm_hip_pattern_window)
+    uint32_t* d_win = nullptr;  // in allocs
     std::string cache_dir;   // compiled-image cache (else $PM_IMAGE_CACHE)
     bool cache_hit = false;
     std::vector<void*> allocs;
@@ -1394,6 +1401,8 @@ void pm_hip_free(void* obj) {
     if (o->batch.d_ev) (void)hipFree(o->batch.d_ev);
     if (o->batch.d_nev) (void)hipFree(o->batch.d_nev);
     if (o->batch.d_grp) (void)hipFree(o->batch.d_grp);
+    if (o->batch.d_pos_in) (void)hipFree(o->batch.d_pos_in);
+    if (o->batch.d_pos_out) (void)hipFree(o->batch.d_pos_out);
     if (o->batch.s) (void)hipStreamDestroy(o->batch.s);
     free_pick(o->pick);
     for (PipeSlot& q : o->slot) {
@@ -1816,7 +1825,28 @@ static GroupDev groups_dev(PmHip* o, const uint32_t* d_stream_groups) {
 struct GroupArgs {
     const uint32_t* stream_groups;
     bool all;
+    // the window forms (pm_hip_read_*_windows): the window kernels, and for flows the
+    // byte counts (host, nseg of them; null = all zero, nothing returned)
+    bool windows = false;
+    uint64_t* pos = nullptr;
 };
+
+// -8 before pm_hip_set_windows; -7 where stream masks come without group tables.
+static int windows_check(PmHip* o, const void* stream_groups) {
+    if (!o->d_win) {
+        std::snprintf(g_err, sizeof(g_err), "pm_hip_set_windows was not called: a window scan needs the window table");
+        return -8;
+    }
+    if (stream_groups && !o->d_gmask) {
+        std::snprintf(g_err, sizeof(g_err), "pm_hip_set_groups was not called: stream masks need the group tables");
+        return -7;
+    }
+    return 0;
+}
+
+static WinDev windows_dev(PmHip* o, const uint64_t* d_pos_in, uint64_t* d_pos_out) {
+    return WinDev{reinterpret_cast<const uint4*>(o->d_win), d_pos_in, d_pos_out};
+}
 
 // The batched events call; all: an event for every pattern ending at a
 // position (pm_hip_scan_batch_matches_device), not only the longest.
@@ -1927,6 +1957,8 @@ uint32_t pm_hip_pattern_len(void* obj, uint32_t gid) {
 // Everything is checked before anything is written.
 // ga (the group forms, pm_hip_read_*_groups): the streams' masks are staged
 // beside the offsets and the group kernels launched; `all` is then ga->all.
+// ga->windows (pm_hip_read_*_windows): the window kernels, and the flows'
+// byte counts staged and written back like the states.
 static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                        uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents,
                        const GroupArgs* ga = nullptr) {
@@ -1950,7 +1982,7 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         return rc;
     if (const int rc = events_gid_check(o)) return rc;
     if (ga)
-        if (const int rc = groups_check(o)) return rc;
+        if (const int rc = ga->windows ? windows_check(o, ga->stream_groups) : groups_check(o)) return rc;
     *nevents = 0;
     if (n == 0) return 0;  // the flow form: every stream keeps its state, which the caller's array holds
     PM_CHECK(hipSetDevice(o->device));
@@ -1976,6 +2008,17 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         PM_CHECK(hipMalloc(&q.d_grp, c * sizeof(uint32_t)));
         q.cap_grp = c;
     }
+    const bool ps = ga && ga->windows && flows && ga->pos;
+    if (ps && nseg > q.cap_pos) {
+        if (q.d_pos_in) PM_CHECK(hipFree(q.d_pos_in));
+        if (q.d_pos_out) PM_CHECK(hipFree(q.d_pos_out));
+        q.d_pos_in = q.d_pos_out = nullptr;
+        q.cap_pos = 0;
+        const size_t c = std::max(nseg, (size_t)1 << 10);
+        PM_CHECK(hipMalloc(&q.d_pos_in, c * sizeof(uint64_t)));
+        PM_CHECK(hipMalloc(&q.d_pos_out, c * sizeof(uint64_t)));
+        q.cap_pos = c;
+    }
     if (!q.d_nev) PM_CHECK(hipMalloc(&q.d_nev, sizeof(unsigned long long)));
     serve_stop(o);  // a device launch wants the whole device
     PM_CHECK(hipMemcpyAsync(q.d_text, buf, n, hipMemcpyHostToDevice, q.s));
@@ -1983,6 +2026,7 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
     if (st) PM_CHECK(hipMemcpyAsync(q.d_st_in, state, nseg * sizeof(uint32_t), hipMemcpyHostToDevice, q.s));
     if (grp)
         PM_CHECK(hipMemcpyAsync(q.d_grp, ga->stream_groups, nseg * sizeof(uint32_t), hipMemcpyHostToDevice, q.s));
+    if (ps) PM_CHECK(hipMemcpyAsync(q.d_pos_in, ga->pos, nseg * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
     size_t dcap = o->events_cap > 0 ? (size_t)o->events_cap : std::max<size_t>(1024, n / 16);
     unsigned long long total = 0;
     for (int launch = 0; launch < 2; ++launch) {
@@ -1999,7 +2043,15 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         const uint32_t* const si = st ? q.d_st_in : nullptr;
         uint32_t* const so = st ? q.d_st_out : nullptr;
         hipError_t e;
-        if (ga) {
+        if (ga && ga->windows) {
+            const GroupDev gr = groups_dev(o, grp ? q.d_grp : nullptr);
+            const WinDev wn = windows_dev(o, ps ? q.d_pos_in : nullptr, ps ? q.d_pos_out : nullptr);
+            e = flows ? pm_launch_dfa_flows_windows(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev,
+                                                    matches_dev(o), gr, wn, ga->all, o->dfa, o->dfa_states,
+                                                    o->flow_seg, o->num_cu, q.s)
+                      : pm_launch_rt_batch_windows(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, matches_dev(o),
+                                                   gr, wn, ga->all, o->rt, o->num_cu, q.s);
+        } else if (ga) {
             const GroupDev gr = groups_dev(o, grp ? q.d_grp : nullptr);
             e = flows ? pm_launch_dfa_flows_groups(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev,
                                                    matches_dev(o), gr, ga->all, o->dfa, o->dfa_states, o->flow_seg,
@@ -2019,7 +2071,7 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(q.s);
             std::snprintf(g_err, sizeof(g_err), "%s %s launch: %s", flows ? "flow" : "batch",
-                          ga ? "groups" : all ? "matches" : "events", hipGetErrorString(e));
+                          ga ? (ga->windows ? "windows" : "groups") : all ? "matches" : "events", hipGetErrorString(e));
             return -3;
         }
         PM_CHECK(hipMemcpyAsync(&total, q.d_nev, sizeof(total), hipMemcpyDeviceToHost, q.s));
@@ -2032,6 +2084,7 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
     std::vector<uint64_t> ev((size_t)total);
     if (total) PM_CHECK(hipMemcpyAsync(ev.data(), q.d_ev, ev.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
     if (st) PM_CHECK(hipMemcpyAsync(state, q.d_st_out, nseg * sizeof(uint32_t), hipMemcpyDeviceToHost, q.s));
+    if (ps) PM_CHECK(hipMemcpyAsync(ga->pos, q.d_pos_out, nseg * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
     PM_CHECK(hipStreamSynchronize(q.s));
     // position order: the position is the high bits; all: then the gid within a position
     std::sort(ev.begin(), ev.end());
@@ -2175,6 +2228,128 @@ int pm_hip_read_flows_groups(void* obj, const uint8_t* buf, const int64_t* offse
     return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents, &ga);
 }
 
+// ---- pattern windows (pm_hip.h, "pattern windows") ---------------------------
+// The table of pm_window_tables on the device, allocated by the first call and
+// overwritten in place by a later one, like the group tables.
+int pm_hip_set_windows(void* obj, const uint32_t* min_start, const uint32_t* max_end, size_t n) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    bool ok = min_start && max_end && n == o->pats.size();
+    for (size_t k = 0; ok && k < n; ++k) ok = min_start[k] <= 0x7FFFFFFFu;
+    if (!ok) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (min_start and max_end required, n == the %zu patterns added, min_start <= "
+                      "0x7FFFFFFF)",
+                      o->pats.size());
+        return -2;
+    }
+    PmParents par;
+    par.parent = o->parent;
+    par.depth = o->depth;
+    PmWindowTables t = pm_window_tables(o->gids, par, min_start, max_end);
+    PM_CHECK(hipSetDevice(o->device));
+    const size_t bytes = t.win.size() * sizeof(uint32_t);
+    if (!o->d_win) {
+        o->d_win = (uint32_t*)dalloc_copy(o, t.win.data(), bytes);
+    } else {
+        PM_CHECK(hipDeviceSynchronize());  // the caller has no window scan in flight; nor has this object now
+        PM_CHECK(hipMemcpy(o->d_win, t.win.data(), bytes, hipMemcpyHostToDevice));
+    }
+    o->win = std::move(t.win);
+    return 0;
+}
+
+int pm_hip_pattern_window(void* obj, uint32_t gid, uint32_t* min_start, uint32_t* max_end) {
+    PmHip* o = as(obj);
+    if (gid == 0 || (size_t)gid * 4 + 3 >= o->win.size() || gid >= o->gids.len.size()) return -1;
+    if (min_start) *min_start = o->win[4 * (size_t)gid] - o->gids.len[gid];
+    if (max_end) *max_end = o->win[4 * (size_t)gid + 1];
+    return 0;
+}
+
+int pm_hip_scan_batch_windows_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                     int64_t n, const uint32_t* d_stream_groups, uint32_t min_len, int all,
+                                     uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                     void* hip_stream) {
+    PmHip* o = as(obj);
+    if (const int rc = batch_check(o)) return rc;
+    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) ||
+        ((uintptr_t)d_stream_groups & 3) || (nseg > 0 && n > 0 && (!d_text || !d_offsets))) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned, stream groups 4-B "
+                      "aligned)");
+        return -2;
+    }
+    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
+    if (const int rc = events_gid_check(o)) return rc;
+    if (const int rc = windows_check(o, d_stream_groups)) return rc;
+    if (nseg == 0 || n == 0) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess)
+        e = pm_launch_rt_batch_windows(d_text, d_offsets, nseg, n, events_dev(o, min_len, d_events, cap, d_nevents),
+                                       matches_dev(o), groups_dev(o, d_stream_groups),
+                                       windows_dev(o, nullptr, nullptr), all != 0, o->rt, o->num_cu,
+                                       (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "batch windows launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_RT;
+    o->last_form = 0;
+    return 0;
+}
+
+int pm_hip_scan_flows_windows_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                     int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out,
+                                     const uint32_t* d_stream_groups, uint32_t min_len, int all, uint64_t* d_events,
+                                     uint64_t cap, unsigned long long* d_nevents, void* hip_stream,
+                                     const uint64_t* d_pos_in, uint64_t* d_pos_out) {
+    PmHip* o = as(obj);
+    if (const int rc = flows_check(o)) return rc;
+    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_state_in & 3) ||
+        ((uintptr_t)d_state_out & 3) || ((uintptr_t)d_stream_groups & 3) || ((uintptr_t)d_pos_in & 7) ||
+        ((uintptr_t)d_pos_out & 7) || (d_state_in && d_state_in == d_state_out) ||
+        (d_pos_in && d_pos_in == d_pos_out) || (nseg > 0 && (!d_offsets || (n > 0 && !d_text)))) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets and positions 8-B aligned, states "
+                      "and stream groups 4-B aligned, state_in != state_out, pos_in != pos_out)");
+        return -2;
+    }
+    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
+    if (const int rc = events_gid_check(o)) return rc;
+    if (const int rc = windows_check(o, d_stream_groups)) return rc;
+    if (nseg == 0 || (n == 0 && !d_state_out && !d_pos_out)) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess)
+        e = pm_launch_dfa_flows_windows(d_text, d_offsets, nseg, n, d_state_in, d_state_out,
+                                        events_dev(o, min_len, d_events, cap, d_nevents), matches_dev(o),
+                                        groups_dev(o, d_stream_groups), windows_dev(o, d_pos_in, d_pos_out), all != 0,
+                                        o->dfa, o->dfa_states, o->flow_seg, o->num_cu, (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "flow windows launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_AC;
+    o->last_form = 1;
+    return 0;
+}
+
+int pm_hip_read_batch_windows(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg,
+                              const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
+                              size_t* nevents) {
+    const GroupArgs ga{stream_groups, all != 0, true, nullptr};
+    return read_events(as(obj), false, true, buf, offsets, nseg, nullptr, min_len, events, cap, nevents, &ga);
+}
+
+int pm_hip_read_flows_windows(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                              uint64_t* pos, const uint32_t* stream_groups, uint32_t min_len, int all,
+                              uint64_t* events, size_t cap, size_t* nevents) {
+    const GroupArgs ga{stream_groups, all != 0, true, pos};
+    return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents, &ga);
+}
+
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,
                         unsigned long long* d_counts, void* hip_stream) {
     PmHip* o = as(obj);
@@ -2232,6 +2407,7 @@ size_t pm_hip_scratch_bytes(void* obj) {
     if (o->batch.d_st_in) b += 2 * o->batch.cap_st * sizeof(uint32_t);
     if (o->batch.d_ev) b += o->batch.cap_ev * sizeof(uint64_t) + sizeof(unsigned long long);
     if (o->batch.d_grp) b += o->batch.cap_grp * sizeof(uint32_t);
+    if (o->batch.d_pos_in) b += 2 * o->batch.cap_pos * sizeof(uint64_t);
     return b;
 }
 
@@ -2664,6 +2840,40 @@ int pm_flat_expand_groups(void* handle, const uint32_t* gids, size_t n, const in
     if (h->par.parent.size() > ((size_t)1 << 24)) return -4;  // a gid has an event's low 24 bits
     const PmGroupTables t = pm_group_tables(h->g, h->par, groups_by_index);
     pm_expand_groups(h->g, h->par, t, gids, n, offsets, nseg, stream_groups, min_len, all != 0, events, cap, nevents);
+    return 0;
+}
+
+// The table pm_hip_set_windows uploads, from the same builder: 4 u32 per gid.
+int pm_flat_window_tables(void* handle, const uint32_t* min_start_by_index, const uint32_t* max_end_by_index, size_t n,
+                          uint32_t* win_out) {
+    PmFlatHandle* h = static_cast<PmFlatHandle*>(handle);
+    if (!min_start_by_index || !max_end_by_index || n != h->g.gid_of_index.size() || !win_out) return -2;
+    for (size_t k = 0; k < n; ++k)
+        if (min_start_by_index[k] > 0x7FFFFFFFu) return -2;
+    const PmWindowTables t = pm_window_tables(h->g, h->par, min_start_by_index, max_end_by_index);
+    std::memcpy(win_out, t.win.data(), t.win.size() * sizeof(uint32_t));
+    return 0;
+}
+
+// The window kernels' contract over n dense gids on the host (pm_expand_windows).
+int pm_flat_expand_windows(void* handle, const uint32_t* gids, size_t n, const int64_t* offsets, size_t nseg,
+                           const uint64_t* pos_in, const uint32_t* stream_groups, const uint32_t* groups_by_index,
+                           const uint32_t* min_start_by_index, const uint32_t* max_end_by_index, uint32_t min_len,
+                           int all, uint64_t* events, size_t cap, size_t* nevents) {
+    PmFlatHandle* h = static_cast<PmFlatHandle*>(handle);
+    if (min_len == 0 || n > ((size_t)1 << 40) || !nevents || (n && !gids) || (cap && !events) || !min_start_by_index ||
+        !max_end_by_index || (nseg && !offsets) || (stream_groups && !groups_by_index))
+        return -2;
+    for (size_t j = 0; j < nseg; ++j)
+        if (offsets[j] > offsets[j + 1]) return -2;
+    for (size_t k = 0; k < h->g.gid_of_index.size(); ++k)
+        if (min_start_by_index[k] > 0x7FFFFFFFu) return -2;
+    if (h->par.parent.size() > ((size_t)1 << 24)) return -4;  // a gid has an event's low 24 bits
+    const PmWindowTables wt = pm_window_tables(h->g, h->par, min_start_by_index, max_end_by_index);
+    PmGroupTables gt;
+    if (groups_by_index) gt = pm_group_tables(h->g, h->par, groups_by_index);
+    pm_expand_windows(h->g, h->par, groups_by_index ? &gt : nullptr, wt, gids, n, offsets, nseg, pos_in, stream_groups,
+                      min_len, all != 0, events, cap, nevents);
     return 0;
 }
 

@@ -149,11 +149,14 @@ class FlowTable:
         flows.end(key)                                    # the flow is over
 
     A key seen for the first time starts a fresh flow.  A key may appear once
-    per scan(): two packets of one flow are concatenated by the caller."""
+    per scan(): two packets of one flow are concatenated by the caller.
+    Beside the state the table keeps the bytes each flow has had, which
+    scan_windows() counts the patterns' windows from."""
 
     def __init__(self, matcher):
         self.matcher = matcher
         self.states = {}
+        self.bytes = {}  # flow key -> the bytes the flow has had (scan_windows' positions)
 
     def scan(self, packets):
         """packets: a list of (key, bytes-like).  Returns the codes of each
@@ -174,6 +177,7 @@ class FlowTable:
         codes, state = self.matcher.read_flows_codes(data, offs, state)
         for k, s in zip(keys, state.tolist()):
             self.states[k] = s
+        self._advance(keys, offs)
         return [codes[offs[j]:offs[j + 1]] for j in range(len(packets))]
 
     def scan_events(self, packets, min_len=3):
@@ -201,6 +205,27 @@ class FlowTable:
             return self.matcher.read_flows_groups(data, offs, grp, state, min_len, all_matches)
         return self._scan_list([(k, b) for k, b, _ in packets], min_len, read, "scan_groups")
 
+    def scan_windows(self, packets, min_len=3, all_matches=True):
+        """scan_groups() with the patterns' windows (HipMatcher.set_windows)
+        applied at each flow's own byte count: packets is a list of (key,
+        bytes-like) or (key, bytes-like, groups), all of one shape.  The table
+        keeps the bytes every flow has had, whichever scan method saw them,
+        so a window counts from the flow's first byte, not the packet's
+        (HipMatcher.read_flows_windows).  The flows' states advance exactly
+        as in scan()."""
+        grp = None
+        if packets and len(packets[0]) == 3:
+            grp = np.array([g for _, _, g in packets], dtype=np.uint32)
+        pos_in = np.array([self.bytes.get(p[0], 0) for p in packets], dtype=np.uint64)
+
+        def read(data, offs, state, min_len):
+            return self.matcher.read_flows_windows(data, offs, grp, state, pos_in, min_len, all_matches)[:3]
+        return self._scan_list([(p[0], p[1]) for p in packets], min_len, read, "scan_windows")
+
+    def _advance(self, keys, offs):
+        for k, n in zip(keys, np.diff(offs).tolist()):
+            self.bytes[k] = self.bytes.get(k, 0) + n
+
     def _scan_list(self, packets, min_len, read, name):
         keys = [k for k, _ in packets]
         if len(set(keys)) != len(keys):
@@ -218,11 +243,13 @@ class FlowTable:
         pos, codes, state = read(data, offs, state, min_len)
         for k, s in zip(keys, state.tolist()):
             self.states[k] = s
+        self._advance(keys, offs)
         return _split_events(pos, codes, offs)
 
     def end(self, key):
         """Forget a flow: its key, seen again, starts a fresh one."""
         self.states.pop(key, None)
+        self.bytes.pop(key, None)
 
     def __len__(self):
         return len(self.states)
@@ -619,6 +646,126 @@ class HipMatcher:
         ev, st = self._read_events(data, offsets, st, min_len, all_matches, stream_groups)
         pos, gids = unpack_events(ev)
         return pos, self._codes[gids], st
+
+    # --- pattern windows: where in its stream a pattern may lie --------------
+    def set_windows(self, min_start, max_end):
+        """pm_hip_set_windows: min_start[k] / max_end[k] (Snort's offset and
+        offset + depth; 0xFFFFFFFF = unbounded) of the k-th pattern added.
+        After compile(); a later call replaces the windows (no window scan
+        may be in flight)."""
+        lo = np.ascontiguousarray(min_start, dtype=np.uint32)
+        hi = np.ascontiguousarray(max_end, dtype=np.uint32)
+        if lo.ndim != 1 or hi.shape != lo.shape:
+            raise ValueError("min_start, max_end: one u32 each per pattern added")
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        rc = self.lib.pm_hip_set_windows(self.obj, lo.ctypes.data_as(u32p), hi.ctypes.data_as(u32p), lo.size)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def pattern_window(self, gid):
+        """(min_start, max_end) of pattern gid; None out of range or before
+        set_windows."""
+        lo, hi = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        if self.lib.pm_hip_pattern_window(self.obj, gid, ctypes.byref(lo), ctypes.byref(hi)) != 0:
+            return None
+        return int(lo.value), int(hi.value)
+
+    def scan_batch_windows_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_stream_groups_ptr, min_len, all_matches,
+                                  d_events_ptr, cap, d_nevents_ptr, stream_ptr):
+        """pm_hip_scan_batch_windows_device: scan_batch_groups_device with a
+        pattern visible only where it also passes its window, counted from
+        its stream's first byte.  Without set_groups every pattern is in
+        every group and d_stream_groups_ptr must be null."""
+        rc = self.lib.pm_hip_scan_batch_windows_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n,
+                                                       d_stream_groups_ptr, min_len, int(bool(all_matches)),
+                                                       d_events_ptr, cap, d_nevents_ptr, stream_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def scan_flows_windows_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr,
+                                  d_stream_groups_ptr, min_len, all_matches, d_events_ptr, cap, d_nevents_ptr,
+                                  stream_ptr, d_pos_in_ptr=None, d_pos_out_ptr=None):
+        """pm_hip_scan_flows_windows_device: scan_flows_groups_device with the
+        windows counted from each flow's own first byte: d_pos_in_ptr holds
+        the bytes every flow had before this call (u64, null = 0),
+        d_pos_out_ptr receives them after it (null = not wanted)."""
+        rc = self.lib.pm_hip_scan_flows_windows_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr,
+                                                       d_state_out_ptr, d_stream_groups_ptr, min_len,
+                                                       int(bool(all_matches)), d_events_ptr, cap, d_nevents_ptr,
+                                                       stream_ptr, d_pos_in_ptr, d_pos_out_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def _read_windows(self, data, offsets, stream_groups, state, pos, min_len, all_matches):
+        """The host window forms: (events u64 ascending, state_out or None,
+        pos_out or None); a short host buffer means one more call, as in
+        _read_events."""
+        arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
+                                   else data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or offs.size < 1 or int(offs[-1]) != len(arr):
+            raise ValueError("offsets: nseg + 1 values, the last one len(data)")
+        nseg = offs.size - 1
+        for name, a in (("state", state), ("pos", pos)):
+            if a is not None and a.shape != (nseg,):
+                raise ValueError(f"{name}: nseg values")
+        grp = None
+        if stream_groups is not None:
+            grp = np.ascontiguousarray(stream_groups, dtype=np.uint32)
+            if grp.shape != (nseg,):
+                raise ValueError("stream_groups: nseg values")
+        u32p, u64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+        cap = max(1024, len(arr) // 16)
+        while True:
+            ev = np.empty(cap, dtype=np.uint64)
+            total = ctypes.c_size_t(0)
+            st = None if state is None else state.copy()
+            ps = None if pos is None else pos.copy()
+            head = (self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                    offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg)
+            tail = (None if grp is None else grp.ctypes.data_as(u32p), min_len, int(bool(all_matches)),
+                    ev.ctypes.data_as(u64p), cap, ctypes.byref(total))
+            if state is None:
+                rc = self.lib.pm_hip_read_batch_windows(*head, *tail)
+            else:
+                rc = self.lib.pm_hip_read_flows_windows(*head, st.ctypes.data_as(u32p),
+                                                        None if ps is None else ps.ctypes.data_as(u64p), *tail)
+            if rc != 0:
+                raise RuntimeError(self.lib.pm_hip_last_error().decode())
+            if total.value <= cap:
+                return ev[:total.value], st, ps
+            cap = total.value
+
+    def read_batch_windows(self, data, offsets, stream_groups=None, min_len=3, all_matches=True):
+        """pm_hip_read_batch_windows: read_batch_groups with the patterns'
+        windows applied (stream_groups None: every stream on all groups):
+        (positions int64, codes), ascending by position, then gid."""
+        ev, _, _ = self._read_windows(data, offsets, stream_groups, None, None, min_len, all_matches)
+        pos, gids = unpack_events(ev)
+        return pos, self._codes[gids]
+
+    def read_many_windows(self, buffers, stream_groups=None, min_len=3, all_matches=True):
+        """read_many_groups with the patterns' windows applied, each buffer a
+        stream of its own."""
+        offs = batch_offsets(buffers)
+        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
+        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        pos, codes = self.read_batch_windows(data, offs, stream_groups, min_len, all_matches)
+        return _split_events(pos, codes, offs)
+
+    def read_flows_windows(self, data, offsets, stream_groups=None, state=None, pos=None, min_len=3,
+                           all_matches=True):
+        """pm_hip_read_flows_windows: read_flows_groups with the patterns'
+        windows applied at pos[j] + (the byte's place in its packet): pos is
+        the bytes every flow had before this call (None: 0).  Returns
+        (positions, codes, state_out, pos_out)."""
+        nseg = len(offsets) - 1
+        st = np.zeros(nseg, dtype=np.uint32) if state is None else np.array(state, dtype=np.uint32, order="C")
+        ps = np.zeros(nseg, dtype=np.uint64) if pos is None else np.array(pos, dtype=np.uint64, order="C")
+        ev, st, ps = self._read_windows(data, offsets, stream_groups, st, ps, min_len, all_matches)
+        p, gids = unpack_events(ev)
+        return p, self._codes[gids], st, ps
 
     # --- flow scan: the batched layout with a carried state per stream -----
     def scan_flows_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr, d_out_ptr,
