@@ -475,6 +475,101 @@ int pm_hip_read_flows_windows(void* obj, const uint8_t* buf, const int64_t* offs
                               uint64_t* pos, const uint32_t* stream_groups, uint32_t min_len, int all,
                               uint64_t* events, size_t cap, size_t* nevents);
 
+/*
+ * Nocase: a per-pattern case-insensitivity flag (Snort's and Suricata's
+ * `nocase`), honoured exactly inside the batched and the flow match-list
+ * scans, beside the group and window tests.  One automaton is built over the
+ * case-FOLDED patterns and walked over case-folded text; a case-sensitive
+ * pattern is then confirmed in the kernel against the real bytes.
+ * Folding: fold(c) = c + 32 for 'A' <= c <= 'Z', else c -- ASCII only: 0x40,
+ * 0x5B, 0x60, 0x7B and bytes >= 0x80 are themselves; a byte "is upper" iff it
+ * lies in 'A'..'Z'.
+ * Pattern h (bytes p, L of them) ENDS at position i of a stream iff the
+ * stream has at least L bytes through i and, for the L bytes t ending at i,
+ * fold(t[k]) == fold(p[k]) for all k where nocase[h] != 0, t[k] == p[k] for
+ * all k where it is 0.  For a flow the earlier calls' bytes count: a pattern
+ * that straddles a packet boundary is found.  h is VISIBLE at i of stream j
+ * iff it ends there, has at least min_len bytes, and -- where
+ * pm_hip_set_groups was called -- groups[h] & stream_groups[j] != 0, and --
+ * where pm_hip_set_windows was called -- it passes its window there (E as in
+ * "pattern windows").  Both tables are optional here.
+ *   all != 0: one event i << 24 | gid(h) per visible h.
+ *   all == 0: at most one event per position, the longest visible pattern;
+ *     among visible patterns of equal length the smallest gid.
+ * Gids are the object's own, one per byte string as added: "GET" and "get"
+ * stay two patterns with two gids and each may be of either kind.  A byte
+ * string added twice has the flag of the add that wins.
+ * pm_hip_set_nocase(obj, nocase, n): after compile() (-1 before); -2 for a
+ * wrong n or NULL.  Builds the images of the folded dictionary for the images
+ * the object holds (the reverse trie for rt / auto, the dense rows for ac /
+ * auto, both cases' columns holding the same word) with the flattener and
+ * the compiled-image cache of compile(), and uploads them with the class
+ * tables ("nocase"); all of it counts in pm_hip_table_bytes from
+ * then on.  A later call (a rule reload) waits for the device, frees the
+ * earlier tables and builds anew.  An object that never calls it behaves,
+ * allocates and launches exactly as before.
+ * pm_hip_pattern_nocase(obj, gid): 0 / 1; -1 for a gid out of range or
+ * before pm_hip_set_nocase.
+ * pm_hip_nocase_flow_states: the states of the folded automaton.  The flow
+ * form's states are ITS states, a space of their own (0 .. that - 1, 0 =
+ * fresh), not interchangeable with pm_hip_scan_flows_device's; the host form
+ * checks them against this bound.
+ * pm_hip_case_words: W, the u64 words of case history per flow.  A case-
+ * sensitive pattern that began in an earlier packet cannot be confirmed from
+ * this call's bytes; given the folded match, t[k] == p[k] iff both are upper
+ * or neither, so one bit per earlier byte is enough.  W = ceil((Lcs - 1) /
+ * 64), Lcs the longest case-sensitive pattern that holds an ASCII letter (0
+ * if none: both pointers are then ignored).  d_case_in / d_case_out: DEVICE
+ * arrays of nseg * W uint64_t, 8-byte aligned and distinct (-2 if equal);
+ * either may be NULL (in: all zero; out: not wanted).  Bit b of word j * W +
+ * w is 1 iff the byte 64 w + b + 1 places before stream j's first byte of
+ * this call was upper; d_case_out is the same window moved on by the
+ * stream's bytes (old bits move up where the packet is shorter than 64 W; an
+ * empty packet copies its words, also in the n == 0 copy pass).
+ * The scan calls take the arguments of the window siblings plus, for flows,
+ * the two histories; return codes, alignment, memory safety, cursor and cap
+ * rules, the nseg == 0 / n == 0 cases and capturability (nothing is
+ * allocated) are theirs.  One new code, -9: pm_hip_set_nocase was not
+ * called.  -7: stream masks without group tables; -6: the object's kind has
+ * no folded image for this scan (or the folded dictionary is past the
+ * reverse-trie encoding).  d_pos_in / d_pos_out are used only where windows
+ * are set.  The flow call launches a second small kernel for d_case_out.
+ * The host forms work like pm_hip_read_*_windows; case_hist is a HOST array
+ * of nseg * W uint64_t read and overwritten like state and pos (NULL = all
+ * zero, nothing returned).
+ * pm_hip_nocase_stats: wall ms of the last pm_hip_set_nocase as a whole and
+ * of its uploads, and the table bytes it added; -1 before it.
+ * Measured (64 MiB, all form, min_len 3, every window unbounded, fresh flows;
+ * profiles/nocase/), over the window call of the same run: with every pattern
+ * nocase (no confirmation; a list 4.3-4.5x as long on random ASCII) 1.29-1.41x
+ * batched and 1.37-1.41x flow on ASCII, 1.14-1.16x and 1.38-1.40x on the lines
+ * stream; with no pattern nocase (the window call's list, 0.25-0.33
+ * confirmations per byte on lines) 1.40-1.51x and 1.60-1.67x on ASCII,
+ * 1.59-1.65x and 4.95-6.00x on lines.  pm_hip_set_nocase takes 0.45-0.89 s
+ * and adds 518-737 MB (snort, merged: the folded dense rows).
+ */
+int pm_hip_set_nocase(void* obj, const uint8_t* nocase, size_t n);
+int pm_hip_pattern_nocase(void* obj, uint32_t gid);
+uint32_t pm_hip_nocase_flow_states(void* obj);
+uint32_t pm_hip_case_words(void* obj);
+int pm_hip_nocase_stats(void* obj, double* build_ms, double* upload_ms, size_t* table_bytes);
+int pm_hip_scan_batch_nocase_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_stream_groups, uint32_t min_len, int all,
+                                    uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                    void* hip_stream);
+int pm_hip_scan_flows_nocase_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out,
+                                    const uint32_t* d_stream_groups, uint32_t min_len, int all, uint64_t* d_events,
+                                    uint64_t cap, unsigned long long* d_nevents, void* hip_stream,
+                                    const uint64_t* d_pos_in, uint64_t* d_pos_out, const uint64_t* d_case_in,
+                                    uint64_t* d_case_out);
+int pm_hip_read_batch_nocase(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg,
+                             const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
+                             size_t* nevents);
+int pm_hip_read_flows_nocase(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                             uint64_t* pos, uint64_t* case_hist, const uint32_t* stream_groups, uint32_t min_len,
+                             int all, uint64_t* events, size_t cap, size_t* nevents);
+
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,
  * PatternsTree.c:485-494): per position, equal -> success; d_algo's pattern
@@ -735,6 +830,30 @@ int pm_flat_expand_windows(void* handle, const uint32_t* gids, size_t n, const i
                            const uint64_t* pos_in, const uint32_t* stream_groups, const uint32_t* groups_by_index,
                            const uint32_t* min_start_by_index, const uint32_t* max_end_by_index, uint32_t min_len,
                            int all, uint64_t* events, size_t cap, size_t* nevents);
+/* Nocase on the host (above).  pm_flat_build_nocase: pm_flat_build_cached of
+ * the same patterns (identical gids, and every array it serves) plus the
+ * image of the folded dictionary of the same kind and the class tables for
+ * the flags (one byte per pattern in add order); pm_flat_array then also
+ * serves "nc_head" "nc_cnext" "nc_cword" "nc_flen" (u32), "nc_pool" "nc_flag"
+ * (u8) and "nc_info" (u32 {max_chain, W, Lcs, folded patterns, folded short
+ * gids, folded flow states}).
+ * pm_flat_host_scan_nocase: the contract of the nocase scans over that
+ * handle -- the batched semantics on a kind-1 image (state / pos / case
+ * arrays ignored), the flow semantics on a kind-2 image, with the device's
+ * folded state numbers and history words.  state_in / pos_in / case_in may
+ * be NULL (fresh / 0 / zero), the out arrays NULL (not wanted) or the in
+ * arrays themselves.  groups_by_index and the two window arrays are optional
+ * (NULL: no such table; stream_groups without groups_by_index is -2).
+ * Output rules and return codes as pm_flat_expand_windows; -1 on a handle of
+ * pm_flat_build, or a kind-1 image that does not fit. */
+void* pm_flat_build_nocase(const char* const* pats, const uint32_t* lens, const uint8_t* nocase, size_t n, int kind,
+                           const char* cache_dir);
+int pm_flat_host_scan_nocase(void* handle, const uint8_t* text, const int64_t* offsets, size_t nseg,
+                             const uint32_t* state_in, uint32_t* state_out, const uint64_t* pos_in, uint64_t* pos_out,
+                             const uint64_t* case_in, uint64_t* case_out, const uint32_t* stream_groups,
+                             const uint32_t* groups_by_index, const uint32_t* min_start_by_index,
+                             const uint32_t* max_end_by_index, uint32_t min_len, int all, uint64_t* events, size_t cap,
+                             size_t* nevents);
 void pm_flat_free(void* handle);
 
 #ifdef __cplusplus

@@ -26,7 +26,10 @@ interface:
                     FlowTable.scan_groups), and their window forms: where in
                     its stream a pattern may lie, Snort's offset and depth
                     (HipMatcher.set_windows, read_*_windows /
-                    scan_*_windows_device, FlowTable.scan_windows)
+                    scan_*_windows_device, FlowTable.scan_windows), and their
+                    nocase forms: a case-insensitivity flag per pattern,
+                    Snort's nocase (HipMatcher.set_nocase, read_*_nocase /
+                    scan_*_nocase_device, FlowTable.scan_nocase)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401

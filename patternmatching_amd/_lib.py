@@ -217,6 +217,35 @@ SIGNATURES = {
                                               c_u32p, c_u32p, ctypes.c_uint32, ctypes.c_int,
                                               ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
                                               ctypes.POINTER(ctypes.c_size_t)]),
+    # per-pattern nocase
+    "pm_hip_set_nocase": (ctypes.c_int, [c_vp, c_u8p, ctypes.c_size_t]),
+    "pm_hip_pattern_nocase": (ctypes.c_int, [c_vp, ctypes.c_uint32]),
+    "pm_hip_nocase_flow_states": (ctypes.c_uint32, [c_vp]),
+    "pm_hip_case_words": (ctypes.c_uint32, [c_vp]),
+    "pm_hip_nocase_stats": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_size_t)]),
+    "pm_hip_scan_batch_nocase_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp,
+                                                       ctypes.c_uint32, ctypes.c_int, c_vp, ctypes.c_uint64, c_vp,
+                                                       c_vp]),
+    "pm_hip_scan_flows_nocase_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int64, ctypes.c_int64, c_vp, c_vp,
+                                                       c_vp, ctypes.c_uint32, ctypes.c_int, c_vp, ctypes.c_uint64,
+                                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pm_hip_read_batch_nocase": (ctypes.c_int, [c_vp, c_u8p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, c_u32p,
+                                                ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "pm_hip_read_flows_nocase": (ctypes.c_int, [c_vp, c_u8p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, c_u32p,
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                                c_u32p, ctypes.c_uint32, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+                                                ctypes.POINTER(ctypes.c_size_t)]),
+    "pm_flat_build_nocase": (c_vp, [ctypes.POINTER(ctypes.c_char_p), c_u32p, c_u8p, ctypes.c_size_t, ctypes.c_int,
+                                    ctypes.c_char_p]),
+    "pm_flat_host_scan_nocase": (ctypes.c_int, [c_vp, c_u8p, ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t,
+                                                c_u32p, c_u32p, ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.POINTER(ctypes.c_uint64), c_u32p, c_u32p, c_u32p, c_u32p,
+                                                ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
 }
 
 _lib = None

@@ -532,6 +532,171 @@ void pm_expand_windows(const PmGidMap& g, const PmParents& par, const PmGroupTab
     *nevents = total;
 }
 
+// ---- per-pattern nocase (pm_flatten.h) ----------------------------------------
+void pm_nocase_fold(const std::vector<std::string>& pats, std::vector<std::string>& fpats,
+                    std::vector<uint32_t>& fidx) {
+    fpats.clear();
+    fidx.assign(pats.size(), 0);
+    std::unordered_map<std::string, uint32_t> seen;
+    seen.reserve(pats.size() * 2 + 1);
+    for (size_t k = 0; k < pats.size(); ++k) {
+        std::string f = pats[k];
+        for (char& c : f) c = (char)pm_fold((uint8_t)c);
+        auto it = seen.find(f);
+        if (it == seen.end()) {
+            it = seen.emplace(f, (uint32_t)fpats.size()).first;
+            fpats.push_back(std::move(f));
+        }
+        fidx[k] = it->second;
+    }
+}
+
+PmNocaseTables pm_nocase_tables(const std::vector<std::string>& pats, const PmGidMap& g, const uint8_t* nocase_by_index,
+                                const std::vector<uint32_t>& fidx, const PmGidMap& fg, const PmParents& fpar) {
+    const size_t G = g.index_of_gid.size(), F = fg.index_of_gid.size();
+    PmNocaseTables t;
+    t.head.assign(F, 0);
+    t.cnext.assign(G, 0);
+    t.cword.assign(G, 0);
+    t.flag.assign(G, 0);
+    t.pool.assign(1, 0);
+    // the add that wins a byte string: the last one (pm_assign_gids)
+    std::unordered_map<std::string, uint32_t> last;
+    last.reserve(pats.size() * 2 + 1);
+    for (size_t k = 0; k < pats.size(); ++k) last[pats[k]] = (uint32_t)k;
+    std::vector<uint32_t> tail(F, 0), members(F, 0);  // per class: its largest gid so far, its size
+    for (size_t q = 1; q < G; ++q) {  // ascending gid
+        const uint32_t k = g.index_of_gid[q];
+        const std::string& p = pats[k];
+        t.flag[q] = nocase_by_index[k] ? 1 : 0;
+        if (last[p] != k) continue;  // shadowed: in no class
+        const uint32_t f = fg.gid_of_index[fidx[k]];
+        if (!t.head[f]) t.head[f] = (uint32_t)q;
+        else t.cnext[tail[f]] = (uint32_t)q;
+        tail[f] = (uint32_t)q;
+        ++members[f];
+        bool letter = false;
+        for (unsigned char c : p) letter |= pm_is_upper(c) || (c >= 'a' && c <= 'z');
+        if (!t.flag[q] && letter) {
+            t.cword[q] = (uint32_t)t.pool.size();  // 1 + the offset past pool[0]
+            t.pool.insert(t.pool.end(), p.begin(), p.end());
+            t.lcs = std::max(t.lcs, (uint32_t)p.size());
+        }
+    }
+    t.W = t.lcs > 1 ? (t.lcs - 1 + 63) / 64 : 0;
+    // past a class's last member: the head of the folded parent's class; chain lengths, parents first
+    std::vector<uint32_t> order(F);
+    for (size_t f = 0; f < F; ++f) order[f] = (uint32_t)f;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return fpar.depth[a] < fpar.depth[b]; });
+    std::vector<uint32_t> chain(F, 0);
+    for (uint32_t f : order)
+        if (f) {
+            const uint32_t up = fpar.parent[f];
+            if (tail[f]) t.cnext[tail[f]] = t.head[up];
+            chain[f] = members[f] + chain[up];
+            t.max_chain = std::max(t.max_chain, chain[f]);
+        }
+    // a link says whether its target needs the case check, so a walk loads cword only then
+    for (uint32_t& x : t.head)
+        if (x && t.cword[x]) x |= PM_NC_CHECK;
+    for (uint32_t& x : t.cnext)
+        if (x && t.cword[x]) x |= PM_NC_CHECK;
+    return t;
+}
+
+void pm_nocase_dup_rows(DfaImage& d) {
+    for (size_t s = 0; s < d.states; ++s)
+        for (uint32_t c = 'A'; c <= 'Z'; ++c) d.next[s * 256 + c] = d.next[s * 256 + c + 32];
+}
+
+std::vector<uint32_t> pm_nocase_gram3(const std::vector<std::string>& fpats) {
+    std::vector<uint32_t> g3((1u << 24) / 32, 0u);
+    for (const std::string& pt : fpats)
+        for (size_t i = 0; i + 3 <= pt.size(); ++i) {
+            uint8_t b[3][2];
+            for (int k = 0; k < 3; ++k) {
+                b[k][0] = b[k][1] = (uint8_t)pt[i + k];
+                if (b[k][0] >= 'a' && b[k][0] <= 'z') b[k][1] = (uint8_t)(b[k][0] - 32);
+            }
+            for (int v = 0; v < 8; ++v) {
+                const uint32_t x = b[0][v & 1] | (uint32_t)b[1][(v >> 1) & 1] << 8 | (uint32_t)b[2][(v >> 2) & 1] << 16;
+                g3[x >> 5] |= 1u << (x & 31);
+            }
+        }
+    return g3;
+}
+
+void pm_expand_nocase(const PmGidMap& g, const PmNocaseTables& nc, const PmGroupTables* gt, const PmWindowTables* wt,
+                      const uint8_t* text, const uint32_t* fgids, size_t n, const int64_t* offsets, size_t nseg,
+                      const uint64_t* pos_in, const uint64_t* case_in, const uint32_t* stream_groups, uint32_t min_len,
+                      bool all, uint64_t* events, size_t cap, size_t* nevents) {
+    size_t total = 0, j = 0;
+    std::vector<uint64_t> one;
+    for (size_t k = 0; k < n && nseg; ++k) {
+        while (j + 1 < nseg && offsets[j + 1] <= (int64_t)k) ++j;
+        const uint32_t f = fgids[k];
+        if (f == 0 || f >= nc.head.size()) continue;
+        const uint32_t sm = gt && stream_groups ? stream_groups[j] : 0xFFFFFFFFu;
+        const uint64_t E = (pos_in ? pos_in[j] : 0) + (uint64_t)k - (uint64_t)offsets[j] + 1;
+        one.clear();
+        uint32_t h = nc.head[f] & ~PM_NC_CHECK;
+        for (uint32_t d = nc.max_chain; d > 0 && h != 0 && g.len[h] >= min_len; --d, h = nc.cnext[h] & ~PM_NC_CHECK) {
+            if (gt && !(gt->gmask[h] & sm)) continue;
+            if (wt) {
+                const uint32_t* w = &wt->win[4 * (size_t)h];
+                if (E < w[0] || (w[1] != 0xFFFFFFFFu && E > w[1])) continue;
+            }
+            if (nc.cword[h]) {
+                const uint8_t* p = &nc.pool[nc.cword[h]];
+                const uint32_t L = g.len[h];
+                bool ok = true;
+                for (uint32_t q = 0; ok && q < L; ++q) {
+                    const int64_t at = (int64_t)k - (int64_t)(L - 1 - q);  // the text position of p[q]
+                    if (at >= offsets[j]) {
+                        ok = text[at] == p[q];
+                    } else {
+                        const uint64_t back = (uint64_t)(offsets[j] - at) - 1;  // bit number in the history
+                        const bool up = case_in && back < 64ull * nc.W &&
+                                        ((case_in[j * nc.W + back / 64] >> (back % 64)) & 1u);
+                        ok = up == pm_is_upper(p[q]);
+                    }
+                }
+                if (!ok) continue;
+            }
+            one.push_back((uint64_t)k << 24 | h);
+            if (!all) break;
+        }
+        std::sort(one.begin(), one.end());
+        for (const uint64_t e : one) {
+            if (total < cap) events[total] = e;
+            ++total;
+        }
+    }
+    *nevents = total;
+}
+
+void pm_nocase_history(const uint8_t* text, const int64_t* offsets, size_t nseg, uint32_t W, const uint64_t* case_in,
+                       uint64_t* case_out) {
+    for (size_t j = 0; j < nseg; ++j) {
+        const int64_t a = offsets[j], b = offsets[j + 1];
+        const uint64_t len = b > a ? (uint64_t)(b - a) : 0;
+        for (uint32_t w = 0; w < W; ++w) {
+            uint64_t v = 0;
+            for (uint32_t bit = 0; bit < 64; ++bit) {
+                const uint64_t back = 64ull * w + bit;  // the byte back + 1 places before the next call's first
+                bool up;
+                if (back < len) up = pm_is_upper(text[b - 1 - (int64_t)back]);
+                else {
+                    const uint64_t old = back - len;
+                    up = case_in && old < 64ull * W && ((case_in[j * W + old / 64] >> (old % 64)) & 1u);
+                }
+                v |= (uint64_t)up << bit;
+            }
+            case_out[j * W + w] = v;
+        }
+    }
+}
+
 // The sparse form (pm_flatten.h).  order: states by depth, so a state's
 // failure (shallower) is decided before it.  The fallback of v is fail[v]
 // when that keeps a row, else fail[v]'s own fallback; then delta(v, c) =

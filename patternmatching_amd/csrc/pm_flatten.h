@@ -203,6 +203,59 @@ void pm_expand_windows(const PmGidMap& g, const PmParents& par, const PmGroupTab
                        const uint32_t* stream_groups, uint32_t min_len, bool all, uint64_t* events, size_t cap,
                        size_t* nevents);
 
+// Per-pattern nocase (pm_hip.h, "nocase").  One automaton is built over the
+// case-folded patterns (ASCII 'A'..'Z' + 32) and walked over case-folded
+// text; its answers are classes of patterns with equal folded bytes, and a
+// case-sensitive member is confirmed against the real bytes.
+//   pm_nocase_fold: fpats = the distinct folded byte strings in first-add
+//     order, fidx[k] = the folded string of pattern k.
+//   pm_nocase_tables, in the patterns' gid space (g) and the folded
+//     dictionary's (fg, fpar), [0] = 0 everywhere:
+//     head[f]   the smallest gid of f's class (the patterns whose folded bytes
+//               are f; a gid shadowed by a later duplicate is in no class)
+//     cnext[q]  the next gid of q's class, ascending; past the last one the
+//               head of the class of f's patterns-tree parent (0: none).
+//               Lengths never rise along it; it takes parent[]'s place in the
+//               chain loops, and max_chain bounds a walk along it
+//     cword[q]  0: no check (nocase, or no ASCII letter); else 1 + the offset
+//               of q's bytes in pool.  A head[] or cnext[] value whose target
+//               has a cword carries PM_NC_CHECK, so a walk knows without a
+//               load whether the member needs the check
+//     flag[q]   nocase_by_index of q's own add
+//     lcs       the longest case-sensitive pattern holding an ASCII letter,
+//     W         ceil((lcs - 1) / 64): the u64 words of case history a flow
+//               carries (bit b of word w: the byte 64 w + b + 1 places before
+//               the call's first byte was 'A'..'Z')
+constexpr uint32_t PM_NC_CHECK = 0x80000000u;
+inline uint8_t pm_fold(uint8_t c) { return c >= 'A' && c <= 'Z' ? (uint8_t)(c + 32) : c; }
+inline bool pm_is_upper(uint8_t c) { return c >= 'A' && c <= 'Z'; }
+void pm_nocase_fold(const std::vector<std::string>& pats, std::vector<std::string>& fpats,
+                    std::vector<uint32_t>& fidx);
+struct PmNocaseTables {
+    std::vector<uint32_t> head, cnext, cword;
+    std::vector<uint8_t> pool, flag;
+    uint32_t max_chain = 0, lcs = 0, W = 0;
+};
+PmNocaseTables pm_nocase_tables(const std::vector<std::string>& pats, const PmGidMap& g, const uint8_t* nocase_by_index,
+                                const std::vector<uint32_t>& fidx, const PmGidMap& fg, const PmParents& fpar);
+// The folded dense rows with the same word in both cases' columns, so a walk
+// over raw text is the walk over folded text.
+void pm_nocase_dup_rows(DfaImage& d);
+// The 3-grams of the folded patterns in every case variant (DfaDev::gram3).
+std::vector<uint32_t> pm_nocase_gram3(const std::vector<std::string>& fpats);
+// The nocase match list on the host (the contract of the nocase kernels) from
+// the folded automaton's dense answers fgids[k] (batched: the reverse walk
+// from each stream's start; flow: the carried folded state).  text holds the
+// real bytes; case_in (nseg * W words, null = zero) answers for the bytes
+// before a stream's first byte, as on the device.  gt / wt null: no table.
+void pm_expand_nocase(const PmGidMap& g, const PmNocaseTables& nc, const PmGroupTables* gt, const PmWindowTables* wt,
+                      const uint8_t* text, const uint32_t* fgids, size_t n, const int64_t* offsets, size_t nseg,
+                      const uint64_t* pos_in, const uint64_t* case_in, const uint32_t* stream_groups, uint32_t min_len,
+                      bool all, uint64_t* events, size_t cap, size_t* nevents);
+// case_out of one call: each stream's history shifted by its bytes.
+void pm_nocase_history(const uint8_t* text, const int64_t* offsets, size_t nseg, uint32_t W, const uint64_t* case_in,
+                       uint64_t* case_out);
+
 // The sparse form with 8-B record units (a device layout, built from the
 // 16-B form at compile time; not cached): rows [0, F) as before, then the
 // records in the same order, each at a unit offset u with state id F + u:

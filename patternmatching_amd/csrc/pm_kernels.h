@@ -221,6 +221,42 @@ hipError_t pm_launch_dfa_flows_windows(const uint8_t* text, const int64_t* offse
                                        const MatchDev& mx, const GroupDev& gr, const WinDev& wn, bool all,
                                        const DfaDev& t, uint32_t states, int64_t force_seg, int num_cu,
                                        hipStream_t s);
+// What the nocase forms add (pm_hip.h, "nocase"; pm_nocase_tables): the
+// tables that lead from an answer of the folded automaton to the patterns of
+// its class and on along the chain, and the case check's bytes.
+//   head[f]   folded gid -> the first gid of its class      flen / fn_short: EvDev's len /
+//   cnext[g]  the next chain member (0: none)                n_short of the folded gids
+//   cword[g]  0, or the offset in pool of the bytes a case-sensitive pattern is confirmed against
+//   a head / cnext value carries bit 31 (PM_NC_CHECK) when its target has a cword
+//   max_chain bounds a walk along cnext whatever it holds
+// W, case_in, case_out (the flow form only): the words of case history per
+// stream, nseg * W of them in and out; nullptr = all zero / not wanted.
+struct NcDev {
+    const uint32_t* head;
+    const uint32_t* cnext;
+    const uint32_t* cword;
+    const uint8_t* pool;
+    const uint32_t* flen;
+    uint32_t fn_short;
+    uint32_t max_chain;
+    uint32_t W;
+    const uint64_t* case_in;
+    uint64_t* case_out;
+};
+// The nocase forms of the window launches (rt_batch_nocase_kernel,
+// dfa_flow_nocase_kernel): t is the image of the FOLDED dictionary (the dense
+// rows with both cases' columns equal), states its state count.  gr.gmask /
+// wn.win == nullptr: the object has no such table (wn.pos_* are then unused).
+// The flow form writes nc.case_out with a second small kernel on the same
+// stream (nocase_history_kernel), also when n == 0.  Arguments, launch shapes
+// and memory safety are the window siblings'; confirmation reads text[0, n).
+hipError_t pm_launch_rt_batch_nocase(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                     const EvDev& ev, const NcDev& nc, const GroupDev& gr, const WinDev& wn, bool all,
+                                     const RtDev& t, int num_cu, hipStream_t s);
+hipError_t pm_launch_dfa_flows_nocase(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                      const uint32_t* state_in, uint32_t* state_out, const EvDev& ev, const NcDev& nc,
+                                      const GroupDev& gr, const WinDev& wn, bool all, const DfaDev& t, uint32_t states,
+                                      int64_t force_seg, int num_cu, hipStream_t s);
 // The sparse kernel (PmSparseKernel) a launch of this width runs, 0 when
 // it runs dense rows: the forced DfaDev::sparse_kernel where the object
 // and width allow it, else the product choice.

@@ -161,14 +161,25 @@ __device__ __forceinline__ uint32_t wide_child(const V4& Q, uint32_t c) {
     return Q.z + (odd ? (uint32_t)__popc(Q.x) : 0u) + (uint32_t)__popc(word & ((1u << bit) - 1u));
 }
 
+// text[k], case-folded (ASCII 'A'..'Z' + 32) when FOLD: the nocase kernels walk the folded
+// reverse trie over the real text with no pass of their own over it.  FOLD == false (every
+// other kernel) is the plain load.
+template <bool FOLD>
+__device__ __forceinline__ uint32_t rt_byte(const uint8_t* __restrict__ text, int64_t k) {
+    uint32_t c = text[k];
+    if (FOLD) c += c - 'A' < 26u ? 32u : 0u;
+    return c;
+}
+
 // Record walk, one position (edge chunks): node = record reached after
 // consuming text[i] .. text[i-d+1]; avail = bytes at or before i.
+template <bool FOLD = false>
 __device__ __forceinline__ uint32_t rt_deep(const uint8_t* __restrict__ text, const RtDev& t, uint32_t node, int64_t i,
                                             int64_t avail, int64_t d) {
     for (;;) {
         const uint4 R = t.rec[node];
         if (d >= avail) return R.y;
-        const uint32_t c = text[i - d];
+        const uint32_t c = rt_byte<FOLD>(text, i - d);
         const uint32_t kind = rec_kind(R), first = R.x & 0xFFFFFFu;
         if (kind == RT_REC_LEAF_K) return R.y;
         if (kind == RT_REC_CHAIN_K) {
@@ -181,7 +192,7 @@ __device__ __forceinline__ uint32_t rt_deep(const uint8_t* __restrict__ text, co
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const uint32_t kk = (uint32_t)k < lim ? (uint32_t)k : lim - 1u;
-                win |= (uint64_t)text[i - d - kk] << (8 * (7 - k));
+                win |= (uint64_t)rt_byte<FOLD>(text, i - d - kk) << (8 * (7 - k));
             }
             const uint64_t dif = win ^ ((uint64_t)R.w << 32 | R.z);
             uint32_t m = dif ? (uint32_t)__builtin_clzll(dif) >> 3 : 8u;
@@ -213,6 +224,7 @@ __device__ __forceinline__ uint32_t rt_slot2(uint32_t k, uint32_t bits) { return
 // best2 = the answer if it stops at depth 2.  The t3h entry of key24 (slot1
 // or slot2) decides depth 3 and, for nodes with at most three children,
 // whether the walk goes on past depth 4.
+template <bool FOLD = false>
 __device__ __forceinline__ uint32_t rt_from_d2(const uint8_t* __restrict__ text, const RtDev& t, uint32_t key24,
                                                uint32_t c3, uint32_t best2, int64_t i, int64_t avail) {
     const uint32_t want = T3H_VALID | key24;
@@ -227,24 +239,25 @@ __device__ __forceinline__ uint32_t rt_from_d2(const uint8_t* __restrict__ text,
         const uint32_t nch = e.z >> 24;
         const uint32_t k = c3 == (e.z & 0xFFu) ? 0u : c3 == ((e.z >> 8) & 0xFFu) ? 1u : c3 == ((e.z >> 16) & 0xFFu) ? 2u : 3u;
         if (k >= nch) return e.y;
-        if (nch > 1) return rt_deep(text, t, e.w + k, i, avail, 4);
+        if (nch > 1) return rt_deep<FOLD>(text, t, e.w + k, i, avail, 4);
         if (!(e.w & CONT32)) return e.w;
-        return rt_deep(text, t, e.w & 0x7FFFFFFFu, i, avail, 4);
+        return rt_deep<FOLD>(text, t, e.w & 0x7FFFFFFFu, i, avail, 4);
     }
-    return rt_deep(text, t, e.w & 0x7FFFFFFFu, i, avail, 3);
+    return rt_deep<FOLD>(text, t, e.w & 0x7FFFFFFFu, i, avail, 3);
 }
 
 // One position, every boundary case (stream start, short lookback).
+template <bool FOLD = false>
 __device__ uint32_t rt_one(const uint8_t* __restrict__ text, const uint16_t* s_t, const RtDev& t, int64_t i,
                            int64_t stream_start) {
     const int64_t avail = i - stream_start + 1;
-    const uint32_t c0 = text[i];
+    const uint32_t c0 = rt_byte<FOLD>(text, i);
     if (avail == 1) return t.t12[65536 + c0];
-    const uint32_t c1 = text[i - 1];
+    const uint32_t c1 = rt_byte<FOLD>(text, i - 1);
     const uint32_t v = s_t[(c0 << 8) | c1];
     if (!(v & CONT16) || avail == 2) return v & 0x7FFFu;
-    return rt_from_d2(text, t, text[i - 2] | (c1 << 8) | (c0 << 16), avail >= 4 ? text[i - 3] : 0u, v & 0x7FFFu, i,
-                      avail);
+    return rt_from_d2<FOLD>(text, t, rt_byte<FOLD>(text, i - 2) | (c1 << 8) | (c0 << 16),
+                            avail >= 4 ? rt_byte<FOLD>(text, i - 3) : 0u, v & 0x7FFFu, i, avail);
 }
 
 // V (ablation, timing only; V=0 is the product kernel):
@@ -2951,6 +2964,387 @@ __global__ __launch_bounds__(DFA_THREADS) __attribute__((amdgpu_waves_per_eu(4))
             }
 }
 
+// ---- per-pattern nocase: case-insensitive patterns in the match-list scans -------
+// The nocase forms of the two window kernels (pm_hip.h, "nocase"): the walk
+// runs over the automaton of the case-folded patterns and sees case-folded
+// text -- the batched kernel folds each byte as it loads it (rt_byte<true>),
+// the flow kernel's folded dense rows hold the same word in both cases'
+// columns, so its walk is the flow kernel's unchanged.  A position's answer f
+// is a gid of the folded dictionary: it is rejected by ev_keep in that gid
+// space (nc.fn_short, nc.flen -- a class shares its length), then mapped to
+// head[f], the first pattern of its class, and the chain runs along cnext[]
+// where the window kernels' runs along parent[]: the class's members by gid,
+// then the class of the folded patterns-tree parent, lengths never rising, so
+// it ends on gid 0 or the length test and the first emit of the longest form
+// is the longest visible pattern, the smallest gid among equals.  A member is
+// visible iff it passes its own group mask and window (the per-pattern halves
+// of the entries; either table may be absent, uniform branches) and, where
+// cword[h] != 0 -- a case-sensitive pattern holding a letter -- its bytes in
+// the pool equal the text's.  The chain folds (reach, the window folds) prune
+// along parent[] and are not used here.
+// Confirmation is a per-lane loop outside every ballot: emit is final before
+// the wave meets again, so ev_reserve / ev_flush see all 64 lanes as before.
+// The batched kernel's match lies inside [start, i] (the walk never crosses
+// start) and the compare checks that again, so every read is in text[0, i].
+// The flow kernel compares the bytes at or after the stream's first byte of
+// this call (clamped at 0) with the text, which may lie before the lane's own
+// segment, and the earlier ones by case alone against the stream's history
+// words: given the folded match, t == p iff both are upper or neither.  A
+// byte past the 64 W places of history counts as not upper.  The flow kernel
+// picks a slot's gid by 16 selects, not an indexed register read: no scratch.
+constexpr uint32_t NC_CHECK = 0x80000000u;  // pm_flatten.h PM_NC_CHECK: a link whose target has a cword
+// ev_keep in the folded dictionary's gid space: its short gids come first too, and a class
+// shares its length
+__device__ __forceinline__ bool nc_keep(uint32_t f, const NcDev& nc, uint32_t min_len) {
+    if (min_len >= 3) {
+        bool keep = f > nc.fn_short;
+        if (min_len > 3 && keep) keep = nc.flen[f] >= min_len;
+        return keep;
+    }
+    return f != 0u && (min_len <= 1 || nc.flen[f] >= min_len);
+}
+template <bool SMALL, bool ALL>
+__global__ __launch_bounds__(RT_THREADS) void rt_batch_nocase_kernel(const uint8_t* __restrict__ text,
+                                                                     const int64_t* __restrict__ offs, int64_t nseg,
+                                                                     int64_t n, EvDev ev, NcDev nc, GroupDev gr,
+                                                                     WinDev wn, RtDev t) {
+    constexpr int kT12Words = SMALL ? 0 : RT_T2_U16 / 2;
+    constexpr int kStageWords = (RT_THREADS / 64) * RT_EV_STAGE * 2;
+    __shared__ __attribute__((aligned(16))) uint32_t s_lds[kT12Words + kStageWords + RT_BATCH_TILE / 32];
+    uint32_t* const s_mask = s_lds + kT12Words + kStageWords;
+    const uint16_t* s_t = t.t12;
+    const int tid = threadIdx.x;
+    EvWave<RT_EV_STAGE> stage{reinterpret_cast<uint64_t*>(s_lds + kT12Words) + (tid >> 6) * RT_EV_STAGE, 0u};
+    if (!SMALL) {
+        const uint4* src = reinterpret_cast<const uint4*>(t.t12);
+        uint4* dst = reinterpret_cast<uint4*>(s_lds);
+        for (int k = tid; k < RT_T2_U16 * 2 / 16; k += RT_THREADS) dst[k] = src[k];
+        __syncthreads();
+        s_t = reinterpret_cast<const uint16_t*>(s_lds);
+    }
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t T0 = ntiles * (int64_t)blockIdx.x / (int64_t)gridDim.x;
+    const int64_t T1 = ntiles * ((int64_t)blockIdx.x + 1) / (int64_t)gridDim.x;
+    const int64_t noffs = nseg + 1;
+    const bool grp = gr.gmask != nullptr;  // uniform: the object has group tables
+    const bool win = wn.win != nullptr;    // uniform: ... a window table
+    int64_t a = batch_seek(offs, 0, noffs, T0 * RT_BATCH_TILE + 1);
+    for (int64_t T = T0; T < T1; ++T) {
+        const int64_t base = T * RT_BATCH_TILE;
+        const int64_t end = base + RT_BATCH_TILE < n ? base + RT_BATCH_TILE : n;
+        a = batch_seek(offs, a, noffs, base + 1);
+        const int64_t b = batch_seek(offs, a, noffs, end);
+        int64_t start = a > 0 ? (int64_t)rfl64((uint64_t)offs[a - 1]) : 0;
+        bool first = true;  // no stream begins in (base, i]: the lane's stream is a - 1, the tile's first
+        if (b > a) {  // workgroup-uniform
+            __syncthreads();
+            if (tid < RT_BATCH_TILE / 32) s_mask[tid] = 0u;
+            __syncthreads();
+            for (int64_t j = a + tid; j < b; j += RT_THREADS) {
+                const int64_t rel = offs[j] - base;
+                if (rel > 0 && rel < RT_BATCH_TILE) atomicOr(&s_mask[rel >> 5], 1u << (rel & 31));
+            }
+            __syncthreads();
+            int w = tid >> 5;
+            uint32_t m = s_mask[w] & (0xFFFFFFFFu >> (31 - (tid & 31)));
+            while (!m && w > 0) m = s_mask[--w];
+            if (m) {
+                start = base + w * 32 + 31 - __clz(m);
+                first = false;
+            }
+        }
+        const int64_t i = base + tid;
+        uint32_t v = 0;
+        if (i < n) {
+            start = start < 0 ? 0 : start > i ? i : start;
+            v = rt_one<true>(text, s_t, t, i, start);
+        }
+        // all 64 lanes of every wave are here (a lane past n holds v = 0)
+        uint32_t h = 0u;  // the lane's pending chain member, 0 = done
+        uint32_t sm = 0xFFFFFFFFu;
+        // the bytes the lane's stream has had through i (a lane past n: unused)
+        const uint32_t E = win_sat((uint64_t)(i - start) + 1u);
+        const bool k0 = nc_keep(v, nc, ev.min_len);
+        if (__ballot(k0)) {  // wave-uniform
+            if (grp && gr.stream_groups) sm = gr.stream_groups[a < 1 ? 0 : a > nseg ? nseg - 1 : a - 1];
+            if (k0) {
+                h = nc.head[v];
+                if (grp && gr.stream_groups && !first) {
+                    // the stream holding i: the first offset > i, minus one; offs[a - 1] <= base, offs[b] >= end
+                    int64_t j = flow_seek(offs, a, b + 1 < noffs ? b + 1 : noffs, i + 1) - 1;
+                    j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+                    sm = gr.stream_groups[j];
+                }
+            }
+        }
+        if (__ballot(h != 0u)) {
+            for (uint32_t d = 0;;) {  // wave-uniform; round 0 is the heads'
+                bool emit = false;  // h is visible at i
+                const uint32_t hg = h & ~NC_CHECK;  // the member's gid (h: NC_CHECK | gid, as the link gave it)
+                if (h) {
+                    emit = !grp || (gr.gmask[hg] & sm) != 0u;
+                    if (win) {
+                        const uint4 w = wn.win[hg];
+                        emit = emit && E >= w.x && E <= w.y;
+                    }
+                    if (emit && (h & NC_CHECK)) {  // per lane: the pattern's bytes against the text's
+                        const uint32_t L = ev.len[hg];
+                        emit = (int64_t)L <= i - start + 1;
+                        const uint8_t* const p = nc.pool + nc.cword[hg];
+                        for (uint32_t k = 0; emit && k < L; ++k) emit = text[i - (int64_t)(L - 1u - k)] == p[k];
+                    }
+                }
+                const uint64_t em = __ballot(emit);
+                if (em) {
+                    const EvSlot slot = ev_reserve(stage, (uint32_t)__popcll(em), ev);
+                    if (emit) ev_put(stage, slot, wave_prefix(em), (uint64_t)i << PM_EV_GID_BITS | hg, ev);
+                }
+                if (!ALL && emit) h = 0u;
+                if (++d >= nc.max_chain) break;
+                if (h) {
+                    const uint32_t p = nc.cnext[hg];
+                    h = ev_keep(p & ~NC_CHECK, ev) ? p : 0u;  // lengths never rise: the chain ends here
+                }
+                if (!__ballot(h != 0u)) break;
+            }
+        }
+        a = b;
+    }
+    ev_flush(stage, ev);
+}
+
+// slot q's value of r[0 .. 15] for a per-lane q: 16 selects, no indexed register read
+__device__ __forceinline__ uint32_t nc_pick16(const uint32_t (&r)[16], uint32_t q) {
+    uint32_t h = 0u;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) h = (uint32_t)k == q ? r[k] : h;
+    return h;
+}
+
+// Pattern bytes p[0, L) against the L bytes ending at position `at` of a flow whose first byte of
+// this call is position sb (>= 0): the text from sb on, the case history (hist: W words, or null
+// = all zero) before it.
+__device__ __forceinline__ bool nc_confirm_flow(const uint8_t* __restrict__ text, const uint8_t* __restrict__ p,
+                                                uint32_t L, int64_t at, int64_t sb,
+                                                const uint64_t* __restrict__ hist, uint32_t W) {
+    for (uint32_t k = 0; k < L; ++k) {
+        const int64_t x = at - (int64_t)(L - 1u - k);
+        const uint32_t c = p[k];
+        if (x >= sb) {
+            if (text[x] != c) return false;
+        } else {
+            const uint64_t back = (uint64_t)(sb - x) - 1u;
+            const bool up = hist && back < 64ull * W && ((hist[back >> 6] >> (back & 63u)) & 1ull);
+            if (up != (c - 'A' < 26u)) return false;
+        }
+    }
+    return true;
+}
+
+template <bool CODED, bool ALL>
+__global__ __launch_bounds__(DFA_THREADS) __attribute__((amdgpu_waves_per_eu(3))) void dfa_flow_nocase_kernel(
+    const uint8_t* __restrict__ text, const int64_t* __restrict__ offs, int64_t nseg, int64_t n,
+    const uint32_t* __restrict__ state_in, uint32_t* __restrict__ state_out, EvDev ev, NcDev nc, GroupDev gr,
+    WinDev wn, const uint32_t* __restrict__ nxt, const uint32_t* __restrict__ outt, uint32_t states, int64_t warm,
+    int64_t seg_len, const uint32_t* __restrict__ gram3) {
+    __shared__ uint64_t s_stage[(DFA_THREADS / 64) * DFA_EV_STAGE];
+    EvWave<DFA_EV_STAGE> stage{s_stage + (threadIdx.x >> 6) * DFA_EV_STAGE, 0u};
+    const int64_t nlane = (n + seg_len - 1) / seg_len;
+    const int64_t stride = (int64_t)gridDim.x * DFA_THREADS;
+    const int64_t gtid = (int64_t)blockIdx.x * DFA_THREADS + threadIdx.x;
+    const int64_t noffs = nseg + 1;
+    const bool grp = gr.gmask != nullptr;  // uniform: the object has group tables
+    const bool win = wn.win != nullptr;    // uniform: ... a window table
+    auto load_state = [&](int64_t j) -> uint32_t {  // j in [0, nseg)
+        const uint32_t s = state_in ? state_in[j] : 0u;
+        return s < states ? s : 0u;
+    };
+    auto load_mask = [&](int64_t j) -> uint32_t {  // j in [0, nseg)
+        return grp && gr.stream_groups ? gr.stream_groups[j] : 0xFFFFFFFFu;
+    };
+    auto load_pos = [&](int64_t j) -> uint64_t {  // j in [0, nseg)
+        return win && wn.pos_in ? wn.pos_in[j] : 0ull;
+    };
+    for (int64_t sg0 = gtid - (threadIdx.x & 63); sg0 < nlane; sg0 += stride) {  // wave-uniform
+        const int64_t sg = sg0 + (threadIdx.x & 63);
+        int64_t i = 0, hi = 0, end = 0, j = 0;  // a lane without a segment: no step
+        uint32_t s = 0, sm = 0;
+        uint64_t pb = 0;  // pos_in[j] - offs[j]: position p of stream j is its byte pb + p (from 0)
+        if (sg < nlane) {
+            const int64_t lo = sg * seg_len;
+            hi = lo + seg_len < n ? lo + seg_len : n;
+            // the stream holding lo: the first offset > lo, minus one
+            j = flow_seek(offs, 0, noffs, lo + 1) - 1;
+            j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+            int64_t start = offs[j];
+            pb = load_pos(j) - (uint64_t)start;
+            start = start < 0 ? 0 : start > lo ? lo : start;
+            end = offs[j + 1];
+            sm = load_mask(j);
+            int64_t wlo = lo - warm;
+            if (wlo < start) wlo = start;
+            int64_t w = wlo;
+            if (gram3) w = dfa_sync_lo(text, lo, wlo, gram3);  // in [wlo, lo]: never before start
+            s = (w == wlo && wlo == start) ? load_state(j) : 0u;
+            for (int64_t k = w; k < lo; ++k) {
+                const uint32_t v = nxt[(size_t)s * 256 + text[k]];
+                s = CODED ? v & DFA_STATE_MASK : v;
+            }
+            i = lo;
+        }
+        while (__any(i < hi)) {  // wave-uniform: one step of every lane that has positions left
+            const int64_t p0 = i;
+            const uint32_t e0 = win_sat(pb + (uint64_t)p0 + 1u);  // the bytes the step's stream has had through p0
+            uint32_t r[16];
+            uint32_t keep = 0;  // bit q: position p0 + q has a pending chain member r[q]
+            const bool stepped = i < hi;
+            if (stepped) {
+                if ((i & 15) == 0 && i + 16 <= hi && i + 16 <= end) {
+                    const uint4 tw = *reinterpret_cast<const uint4*>(text + i);
+                    const uint32_t W[4] = {tw.x, tw.y, tw.z, tw.w};
+                    uint32_t st[16];
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const uint32_t v = nxt[(size_t)s * 256 + ((W[q >> 2] >> (8 * (q & 3))) & 0xFFu)];
+                        s = CODED ? v & DFA_STATE_MASK : v;
+                        r[q] = CODED ? v >> 20 : 0u;
+                        st[q] = s;
+                    }
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        if (CODED) r[q] = r[q] == DFA_ESC ? outt[st[q]] : r[q];
+                        else r[q] = outt[st[q]];
+                        keep |= (uint32_t)nc_keep(r[q], nc, ev.min_len) << q;
+                    }
+                    i += 16;
+                } else {
+                    const uint32_t v = nxt[(size_t)s * 256 + text[i]];
+                    s = CODED ? v & DFA_STATE_MASK : v;
+                    uint32_t id = CODED ? v >> 20 : outt[s];
+                    if (CODED && id == DFA_ESC) id = outt[s];
+                    r[0] = id;
+                    keep = (uint32_t)nc_keep(id, nc, ev.min_len);
+                    ++i;
+                }
+            }
+            // the folded answers that passed ev_keep: the first pattern of each one's class
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if ((keep >> q) & 1u) r[q] = nc.head[r[q]];
+            // all 64 lanes are here
+            if (__any(keep != 0u)) {
+                for (uint32_t d = 0;;) {  // wave-uniform; round 0 is the heads'
+                    uint32_t emit = 0;  // bit q: r[q] is visible at p0 + q
+                    uint32_t chk = 0;   // ... if its bytes are the text's
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if ((keep >> q) & 1u) {
+                            const uint32_t h = r[q] & ~NC_CHECK;
+                            bool e = !grp || (gr.gmask[h] & sm) != 0u;
+                            if (win) {
+                                const uint4 w = wn.win[h];
+                                const uint32_t E = win_add(e0, (uint32_t)q);
+                                e = e && E >= w.x && E <= w.y;
+                            }
+                            emit |= (uint32_t)e << q;
+                            chk |= (uint32_t)(e && (r[q] & NC_CHECK)) << q;
+                        }
+                    while (chk) {  // per lane, rare: one case-sensitive candidate at a time
+                        const uint32_t q = (uint32_t)__ffs((int)chk) - 1u;
+                        chk &= chk - 1u;
+                        const uint32_t h = nc_pick16(r, q) & ~NC_CHECK;
+                        const uint32_t cw = nc.cword[h];
+                        const int64_t sb = offs[j];  // the stream's first byte of this call
+                        if (!nc_confirm_flow(text, nc.pool + cw, ev.len[h], p0 + q, sb < 0 ? 0 : sb,
+                                             nc.case_in ? nc.case_in + (size_t)j * nc.W : nullptr, nc.W))
+                            emit &= ~(1u << q);
+                    }
+                    if (__any(emit != 0u)) {
+                        const uint32_t c = __popc(emit);
+                        const uint32_t incl = wave_scan_incl(c);
+                        const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
+                        const EvSlot slot = ev_reserve(stage, total, ev);
+                        uint32_t k = incl - c;
+#pragma unroll
+                        for (int q = 0; q < 16; ++q)
+                            if ((emit >> q) & 1u)
+                                ev_put(stage, slot, k++, (uint64_t)(p0 + q) << PM_EV_GID_BITS | (r[q] & ~NC_CHECK), ev);
+                    }
+                    if (!ALL) keep &= ~emit;
+                    if (++d >= nc.max_chain) break;
+                    // r[q] = cnext[r[q]] in place; lengths never rise: a member below min_len ends its chain
+#pragma unroll
+                    for (int q = 0; q < 16; ++q)
+                        if ((keep >> q) & 1u) {
+                            const uint32_t h = nc.cnext[r[q] & ~NC_CHECK];
+                            if (ev_keep(h & ~NC_CHECK, ev)) r[q] = h;
+                            else keep &= ~(1u << q);
+                        }
+                    if (!__any(keep != 0u)) break;
+                }
+            }
+            // after the rounds, which use the step's own stream (j, sm, pb): the step ended stream j
+            if (stepped && i == end) {  // position end - 1 was stream j's last byte
+                if (state_out) state_out[j] = s;
+                if (win && wn.pos_out) wn.pos_out[j] = pb + (uint64_t)end;
+                if (i < hi) {
+                    // the next stream that is not empty: the first offset > i, minus one
+                    j = flow_seek(offs, j + 2 < noffs ? j + 2 : noffs, noffs, i + 1) - 1;
+                    j = j < 0 ? 0 : j > nseg - 1 ? nseg - 1 : j;
+                    pb = load_pos(j) - (uint64_t)offs[j];
+                    end = offs[j + 1];
+                    s = load_state(j);
+                    sm = load_mask(j);
+                }
+            }
+        }
+    }
+    ev_flush(stage, ev);
+    // empty streams keep their state (as used: an invalid one is the root) and their position
+    if (state_out || (win && wn.pos_out))
+        for (int64_t j = gtid; j < nseg; j += stride)
+            if (offs[j + 1] <= offs[j]) {
+                if (state_out) state_out[j] = load_state(j);
+                if (win && wn.pos_out) wn.pos_out[j] = load_pos(j);
+            }
+}
+
+// case_out of a flow call (pm_hip.h, "nocase"): one lane per history word.  Bit b of word w of
+// stream j: the byte 64 w + b + 1 places before the stream's next call was 'A'..'Z' -- a byte of
+// this call's text where the stream brought that many, else the old history moved up by the
+// stream's bytes.  An empty stream copies its words.  Reads stay in text[0, n), offs[0, nseg]
+// and case_in[0, nseg * W) whatever the offsets hold.
+constexpr int NC_HIST_THREADS = 256;
+__global__ __launch_bounds__(NC_HIST_THREADS) void nocase_history_kernel(const uint8_t* __restrict__ text,
+                                                                         const int64_t* __restrict__ offs,
+                                                                         int64_t nseg, int64_t n, uint32_t W,
+                                                                         const uint64_t* __restrict__ case_in,
+                                                                         uint64_t* __restrict__ case_out) {
+    const int64_t total = nseg * (int64_t)W;
+    for (int64_t k = (int64_t)blockIdx.x * NC_HIST_THREADS + threadIdx.x; k < total;
+         k += (int64_t)gridDim.x * NC_HIST_THREADS) {
+        const int64_t j = k / W;
+        const uint32_t w = (uint32_t)(k - j * W);
+        int64_t a = offs[j], b = offs[j + 1];
+        b = b < 0 ? 0 : b > n ? n : b;
+        a = a < 0 ? 0 : a > b ? b : a;
+        const uint64_t len = (uint64_t)(b - a);
+        uint64_t v = 0;
+        for (uint32_t bit = 0; bit < 64; ++bit) {
+            const uint64_t back = 64ull * w + bit;
+            bool up = false;
+            if (back < len) {
+                up = (uint32_t)text[b - 1 - (int64_t)back] - 'A' < 26u;
+            } else if (case_in) {
+                const uint64_t old = back - len;
+                up = old < 64ull * W && ((case_in[j * W + (old >> 6)] >> (old & 63u)) & 1ull);
+            }
+            v |= (uint64_t)up << bit;
+        }
+        case_out[k] = v;
+    }
+}
+
 // The sparse (default-transition) form, pm_flatten.h: rows only for the
 // states whose row differs from their fallback's in more than PM_SDFA_K
 // bytes, 16-B records for the rest (8-B units in pm_pack_sparse8's
@@ -4578,6 +4972,60 @@ hipError_t pm_launch_dfa_flows_windows(const uint8_t* text, const int64_t* offse
                             : (all ? dfa_flow_windows_kernel<false, true> : dfa_flow_windows_kernel<false, false>);
     hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev, mx, gr, wn, t.next, t.out,
                        states, t.warm, seg, g3);
+    return hipGetLastError();
+}
+
+// The nocase forms (rt_batch_nocase_kernel, dfa_flow_nocase_kernel): the window launches over the
+// folded images.  Group and window tables are optional; stream masks only with group tables.
+static bool nocase_args_ok(const EvDev& ev, const NcDev& nc, const GroupDev& gr) {
+    return ev.cursor && ev.len && ev.min_len >= 1 && (ev.events || !ev.cap) && nc.head && nc.cnext && nc.cword &&
+           nc.pool && nc.flen && (gr.gmask || !gr.stream_groups);
+}
+
+hipError_t pm_launch_rt_batch_nocase(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                     const EvDev& ev, const NcDev& nc, const GroupDev& gr, const WinDev& wn, bool all,
+                                     const RtDev& t, int num_cu, hipStream_t s) {
+    if (n <= 0 || nseg <= 0) return hipSuccess;
+    if (!text || !offsets || num_cu <= 0 || !nocase_args_ok(ev, nc, gr)) return hipErrorInvalidValue;
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
+    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
+    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    auto* const k = small ? (all ? rt_batch_nocase_kernel<true, true> : rt_batch_nocase_kernel<true, false>)
+                          : (all ? rt_batch_nocase_kernel<false, true> : rt_batch_nocase_kernel<false, false>);
+    hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, ev, nc, gr, wn, t);
+    return hipGetLastError();
+}
+
+hipError_t pm_launch_dfa_flows_nocase(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
+                                      const uint32_t* state_in, uint32_t* state_out, const EvDev& ev, const NcDev& nc,
+                                      const GroupDev& gr, const WinDev& wn, bool all, const DfaDev& t, uint32_t states,
+                                      int64_t force_seg, int num_cu, hipStream_t s) {
+    const bool hist = nc.W && nc.case_out;
+    const bool pos = wn.win && wn.pos_out;
+    if (nseg <= 0 || n < 0 || (n == 0 && !state_out && !pos && !hist)) return hipSuccess;
+    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
+    if (!nocase_args_ok(ev, nc, gr)) return hipErrorInvalidValue;
+    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
+    if (n > 0 || state_out || pos) {
+        int64_t seg, blocks;
+        if (!flow_shape(nseg, n, 16, force_seg, num_cu, seg, blocks)) return hipErrorInvalidValue;
+        const dim3 g((unsigned)blocks), b(DFA_THREADS);
+        const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
+        auto* const k = t.coded ? (all ? dfa_flow_nocase_kernel<true, true> : dfa_flow_nocase_kernel<true, false>)
+                                : (all ? dfa_flow_nocase_kernel<false, true> : dfa_flow_nocase_kernel<false, false>);
+        hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev, nc, gr, wn, t.next, t.out,
+                           states, t.warm, seg, g3);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (hist) {
+        const int64_t words = nseg * (int64_t)nc.W;
+        int64_t blocks = (words + NC_HIST_THREADS - 1) / NC_HIST_THREADS;
+        if (blocks > (int64_t)num_cu * 8) blocks = (int64_t)num_cu * 8;
+        hipLaunchKernelGGL(nocase_history_kernel, dim3((unsigned)blocks), dim3(NC_HIST_THREADS), 0, s, text, offsets,
+                           nseg, n, nc.W, nc.case_in, nc.case_out);
+    }
     return hipGetLastError();
 }
 

@@ -265,7 +265,24 @@ struct BatchStage {
     uint64_t* d_pos_in = nullptr;
     uint64_t* d_pos_out = nullptr;
     size_t cap_pos = 0;
+    // the flow nocase call's case histories in and out (pm_hip_read_flows_nocase), cap_case words of each
+    uint64_t* d_case_in = nullptr;
+    uint64_t* d_case_out = nullptr;
+    size_t cap_case = 0;
     hipStream_t s = nullptr;
+};
+// Per-pattern nocase (pm_hip_set_nocase): the images of the folded dictionary
+// and the class tables, in allocations of their own (a reload frees them).
+struct Nocase {
+    bool set = false;
+    RtDev rt{};    // rt.t12 == nullptr: no folded reverse trie (the ac kind, or it does not fit)
+    DfaDev dfa{};  // dfa.next == nullptr: no folded dense rows (the rt kind)
+    uint32_t dfa_states = 0;
+    NcDev dev{};
+    std::vector<uint8_t> flag;  // per gid (pm_hip_pattern_nocase)
+    std::vector<void*> allocs;
+    size_t bytes = 0;
+    double build_s = 0.0, upload_s = 0.0;
 };
 struct PmHip {
     int kind_req = KIND_RT;
@@ -293,6 +310,7 @@ struct PmHip {
     // pattern windows (pm_hip_set_windows): nothing before its first call
     std::vector<uint32_t> win;  // host copy of d_win, 4 per gid (pm_hip_pattern_window)
     uint32_t* d_win = nullptr;  // in allocs
+    Nocase nc;  // per-pattern nocase (pm_hip_set_nocase): nothing before its first call
     std::string cache_dir;   // compiled-image cache (else $PM_IMAGE_CACHE)
     bool cache_hit = false;
     std::vector<void*> allocs;
@@ -1386,6 +1404,7 @@ void pm_hip_free(void* obj) {
     (void)hipSetDevice(o->device);
     serve_free(o);  // before the tables it reads
     for (void* p : o->allocs) (void)hipFree(p);
+    for (void* p : o->nc.allocs) (void)hipFree(p);
     if (o->spill) (void)hipFree(o->spill);
     for (StreamSpill& x : o->sspill) {
         if (x.buf) (void)hipFree(x.buf);
@@ -1403,6 +1422,8 @@ void pm_hip_free(void* obj) {
     if (o->batch.d_grp) (void)hipFree(o->batch.d_grp);
     if (o->batch.d_pos_in) (void)hipFree(o->batch.d_pos_in);
     if (o->batch.d_pos_out) (void)hipFree(o->batch.d_pos_out);
+    if (o->batch.d_case_in) (void)hipFree(o->batch.d_case_in);
+    if (o->batch.d_case_out) (void)hipFree(o->batch.d_case_out);
     if (o->batch.s) (void)hipStreamDestroy(o->batch.s);
     free_pick(o->pick);
     for (PipeSlot& q : o->slot) {
@@ -1829,6 +1850,11 @@ struct GroupArgs {
     // byte counts (host, nseg of them; null = all zero, nothing returned)
     bool windows = false;
     uint64_t* pos = nullptr;
+    // the nocase forms (pm_hip_read_*_nocase): the nocase kernels, the group and window tables
+    // where the object has them, and for flows the case histories (host, nseg * W words; null =
+    // all zero, nothing returned)
+    bool nocase = false;
+    uint64_t* case_hist = nullptr;
 };
 
 // -8 before pm_hip_set_windows; -7 where stream masks come without group tables.
@@ -1846,6 +1872,44 @@ static int windows_check(PmHip* o, const void* stream_groups) {
 
 static WinDev windows_dev(PmHip* o, const uint64_t* d_pos_in, uint64_t* d_pos_out) {
     return WinDev{reinterpret_cast<const uint4*>(o->d_win), d_pos_in, d_pos_out};
+}
+
+// -9 before pm_hip_set_nocase; -6 where the kind lacks the folded image the scan walks; -7 where
+// stream masks come without group tables.
+static int nocase_check(PmHip* o, bool flows, const void* stream_groups) {
+    if (!o->nc.set) {
+        std::snprintf(g_err, sizeof(g_err), "pm_hip_set_nocase was not called: a nocase scan needs the folded images");
+        return -9;
+    }
+    if (flows ? !o->nc.dfa.next : !o->nc.rt.t12) {
+        std::snprintf(g_err, sizeof(g_err), "this object holds no folded %s image (its kind, or the folded dictionary "
+                      "is past the reverse-trie encoding)", flows ? "DFA" : "reverse-trie");
+        return -6;
+    }
+    if (stream_groups && !o->d_gmask) {
+        std::snprintf(g_err, sizeof(g_err), "pm_hip_set_groups was not called: stream masks need the group tables");
+        return -7;
+    }
+    return 0;
+}
+
+static NcDev nocase_dev(PmHip* o, const uint64_t* d_case_in, uint64_t* d_case_out) {
+    NcDev d = o->nc.dev;
+    d.case_in = d.W ? d_case_in : nullptr;
+    d.case_out = d.W ? d_case_out : nullptr;
+    return d;
+}
+
+// The folded images with the object's launch options (pm_hip_set_option writes rt / dfa).
+static RtDev nocase_rt(PmHip* o) {
+    RtDev t = o->nc.rt;
+    t.small_max = o->rt.small_max;
+    return t;
+}
+static DfaDev nocase_dfa(PmHip* o) {
+    DfaDev t = o->nc.dfa;
+    t.sync = o->dfa.sync;
+    return t;
 }
 
 // The batched events call; all: an event for every pattern ending at a
@@ -1969,7 +2033,8 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         for (size_t j = 0; ok && j < nseg; ++j) ok = offsets[j] <= offsets[j + 1];
         if (ok && offsets[nseg] > 0) ok = buf != nullptr;
         if (ok && flows && state)
-            for (size_t j = 0; ok && j < nseg; ++j) ok = state[j] < o->dfa_states;
+            for (size_t j = 0; ok && j < nseg; ++j)
+                ok = state[j] < (ga && ga->nocase && o->nc.set ? o->nc.dfa_states : o->dfa_states);
     }
     if (!ok) {
         std::snprintf(g_err, sizeof(g_err), "bad arguments (offsets[0] == 0, offsets non-decreasing%s)",
@@ -1982,7 +2047,10 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         return rc;
     if (const int rc = events_gid_check(o)) return rc;
     if (ga)
-        if (const int rc = ga->windows ? windows_check(o, ga->stream_groups) : groups_check(o)) return rc;
+        if (const int rc = ga->nocase    ? nocase_check(o, flows, ga->stream_groups)
+                           : ga->windows ? windows_check(o, ga->stream_groups)
+                                         : groups_check(o))
+            return rc;
     *nevents = 0;
     if (n == 0) return 0;  // the flow form: every stream keeps its state, which the caller's array holds
     PM_CHECK(hipSetDevice(o->device));
@@ -2008,7 +2076,18 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         PM_CHECK(hipMalloc(&q.d_grp, c * sizeof(uint32_t)));
         q.cap_grp = c;
     }
-    const bool ps = ga && ga->windows && flows && ga->pos;
+    const bool ps = ga && (ga->windows || (ga->nocase && o->d_win)) && flows && ga->pos;
+    const size_t cwords = ga && ga->nocase && flows && ga->case_hist ? nseg * (size_t)o->nc.dev.W : 0;
+    if (cwords > q.cap_case) {
+        if (q.d_case_in) PM_CHECK(hipFree(q.d_case_in));
+        if (q.d_case_out) PM_CHECK(hipFree(q.d_case_out));
+        q.d_case_in = q.d_case_out = nullptr;
+        q.cap_case = 0;
+        const size_t c = std::max(cwords, (size_t)1 << 10);
+        PM_CHECK(hipMalloc(&q.d_case_in, c * sizeof(uint64_t)));
+        PM_CHECK(hipMalloc(&q.d_case_out, c * sizeof(uint64_t)));
+        q.cap_case = c;
+    }
     if (ps && nseg > q.cap_pos) {
         if (q.d_pos_in) PM_CHECK(hipFree(q.d_pos_in));
         if (q.d_pos_out) PM_CHECK(hipFree(q.d_pos_out));
@@ -2027,6 +2106,8 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
     if (grp)
         PM_CHECK(hipMemcpyAsync(q.d_grp, ga->stream_groups, nseg * sizeof(uint32_t), hipMemcpyHostToDevice, q.s));
     if (ps) PM_CHECK(hipMemcpyAsync(q.d_pos_in, ga->pos, nseg * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    if (cwords)
+        PM_CHECK(hipMemcpyAsync(q.d_case_in, ga->case_hist, cwords * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
     size_t dcap = o->events_cap > 0 ? (size_t)o->events_cap : std::max<size_t>(1024, n / 16);
     unsigned long long total = 0;
     for (int launch = 0; launch < 2; ++launch) {
@@ -2043,7 +2124,17 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         const uint32_t* const si = st ? q.d_st_in : nullptr;
         uint32_t* const so = st ? q.d_st_out : nullptr;
         hipError_t e;
-        if (ga && ga->windows) {
+        if (ga && ga->nocase) {
+            const GroupDev gr = o->d_gmask ? groups_dev(o, grp ? q.d_grp : nullptr) : GroupDev{nullptr, nullptr, nullptr};
+            const WinDev wn = o->d_win ? windows_dev(o, ps ? q.d_pos_in : nullptr, ps ? q.d_pos_out : nullptr)
+                                       : WinDev{nullptr, nullptr, nullptr};
+            const NcDev nc = nocase_dev(o, cwords ? q.d_case_in : nullptr, cwords ? q.d_case_out : nullptr);
+            e = flows ? pm_launch_dfa_flows_nocase(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev, nc, gr, wn,
+                                                   ga->all, nocase_dfa(o), o->nc.dfa_states, o->flow_seg, o->num_cu,
+                                                   q.s)
+                      : pm_launch_rt_batch_nocase(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, nc, gr, wn, ga->all,
+                                                  nocase_rt(o), o->num_cu, q.s);
+        } else if (ga && ga->windows) {
             const GroupDev gr = groups_dev(o, grp ? q.d_grp : nullptr);
             const WinDev wn = windows_dev(o, ps ? q.d_pos_in : nullptr, ps ? q.d_pos_out : nullptr);
             e = flows ? pm_launch_dfa_flows_windows(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev,
@@ -2071,7 +2162,8 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(q.s);
             std::snprintf(g_err, sizeof(g_err), "%s %s launch: %s", flows ? "flow" : "batch",
-                          ga ? (ga->windows ? "windows" : "groups") : all ? "matches" : "events", hipGetErrorString(e));
+                          ga ? (ga->nocase ? "nocase" : ga->windows ? "windows" : "groups") : all ? "matches" : "events",
+                          hipGetErrorString(e));
             return -3;
         }
         PM_CHECK(hipMemcpyAsync(&total, q.d_nev, sizeof(total), hipMemcpyDeviceToHost, q.s));
@@ -2085,6 +2177,8 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
     if (total) PM_CHECK(hipMemcpyAsync(ev.data(), q.d_ev, ev.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
     if (st) PM_CHECK(hipMemcpyAsync(state, q.d_st_out, nseg * sizeof(uint32_t), hipMemcpyDeviceToHost, q.s));
     if (ps) PM_CHECK(hipMemcpyAsync(ga->pos, q.d_pos_out, nseg * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    if (cwords)
+        PM_CHECK(hipMemcpyAsync(ga->case_hist, q.d_case_out, cwords * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
     PM_CHECK(hipStreamSynchronize(q.s));
     // position order: the position is the high bits; all: then the gid within a position
     std::sort(ev.begin(), ev.end());
@@ -2350,6 +2444,207 @@ int pm_hip_read_flows_windows(void* obj, const uint8_t* buf, const int64_t* offs
     return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents, &ga);
 }
 
+// ---- per-pattern nocase (pm_hip.h, "nocase") ---------------------------------
+// The images of the folded dictionary for the images the object holds, through
+// the compiled-image cache like compile()'s, and the class tables of
+// pm_nocase_tables.  Every call builds and uploads anew; a later one (a rule
+// reload) first waits for the device and frees the earlier call's tables.
+static void* nc_alloc_copy(PmHip* o, const void* src, size_t bytes) {
+    void* p = nullptr;
+    PM_CHECK(hipMalloc(&p, bytes ? bytes : 16));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (bytes) PM_CHECK(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+    o->nc.upload_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    o->nc.allocs.push_back(p);
+    o->nc.bytes += bytes;
+    o->table_bytes += bytes;
+    return p;
+}
+
+int pm_hip_set_nocase(void* obj, const uint8_t* nocase, size_t n) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    if (!nocase || n != o->pats.size()) {
+        std::snprintf(g_err, sizeof(g_err), "bad arguments (nocase required, n == the %zu patterns added)",
+                      o->pats.size());
+        return -2;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    PM_CHECK(hipSetDevice(o->device));
+    if (o->nc.set) {
+        PM_CHECK(hipDeviceSynchronize());  // the caller has no nocase scan in flight; nor has this object now
+        for (void* p : o->nc.allocs) PM_CHECK(hipFree(p));
+        o->table_bytes -= o->nc.bytes;
+        o->nc = Nocase();
+    }
+    std::vector<std::string> fpats;
+    std::vector<uint32_t> fidx;
+    pm_nocase_fold(o->pats, fpats, fidx);
+    const PmGidMap fg = pm_assign_gids(fpats);
+    const char* env = std::getenv("PM_IMAGE_CACHE");
+    const std::string dir = !o->cache_dir.empty() ? o->cache_dir : (env ? env : "");
+    const bool want_rt = o->kind == KIND_RT || o->kind == KIND_AUTO;
+    const bool want_dfa = o->kind == KIND_AC || o->kind == KIND_AUTO;
+    bool hit = false;
+    PmImages im = pm_build_images_cached(fpats, fg, want_rt ? KIND_RT : KIND_AC, dir, &hit);
+    if (want_rt && want_dfa) {
+        PmImages d = pm_build_images_cached(fpats, fg, KIND_AC, dir, &hit);
+        im.dfa = std::move(d.dfa);
+    }
+    const PmNocaseTables t = pm_nocase_tables(o->pats, o->gids, nocase, fidx, fg, im.par);
+    Nocase& nc = o->nc;
+    if (want_rt && im.rt.fits) {
+        nc.rt = o->rt;  // the scratch and the options; the tables below
+        nc.rt.t12 = (const uint16_t*)nc_alloc_copy(o, im.rt.t12.data(), im.rt.t12.size() * 2);
+        nc.rt.filt = (const uint32_t*)nc_alloc_copy(o, im.rt.filt.data(), im.rt.filt.size() * 4);
+        nc.rt.t3h = (const uint4*)nc_alloc_copy(o, im.rt.t3h.data(), im.rt.t3h.size() * 4);
+        nc.rt.t3h_bits = im.rt.t3h_bits;
+        nc.rt.rec = (const uint4*)nc_alloc_copy(o, im.rt.rec.data(), im.rt.rec.size() * 4);
+        nc.rt.wide = (const uint4*)nc_alloc_copy(o, im.rt.wide.data(), im.rt.wide.size() * 4);
+    }
+    if (want_dfa && !im.dfa.next.empty()) {
+        pm_nocase_dup_rows(im.dfa);
+        nc.dfa = DfaDev{};
+        nc.dfa.next = (const uint32_t*)nc_alloc_copy(o, im.dfa.next.data(), im.dfa.next.size() * 4);
+        nc.dfa.out = (const uint32_t*)nc_alloc_copy(o, im.dfa.out.data(), im.dfa.out.size() * 4);
+        nc.dfa.warm = o->dfa.warm;
+        nc.dfa.coded = pm_dfa_coded(im.dfa.states) ? 1 : 0;
+        if (nc.dfa.warm > 3) {
+            const std::vector<uint32_t> g3 = pm_nocase_gram3(fpats);
+            nc.dfa.gram3 = (const uint32_t*)nc_alloc_copy(o, g3.data(), g3.size() * 4);
+        }
+        nc.dfa_states = im.dfa.states;
+    }
+    nc.dev.head = (const uint32_t*)nc_alloc_copy(o, t.head.data(), t.head.size() * 4);
+    nc.dev.cnext = (const uint32_t*)nc_alloc_copy(o, t.cnext.data(), t.cnext.size() * 4);
+    nc.dev.cword = (const uint32_t*)nc_alloc_copy(o, t.cword.data(), t.cword.size() * 4);
+    nc.dev.pool = (const uint8_t*)nc_alloc_copy(o, t.pool.data(), t.pool.size());
+    nc.dev.flen = (const uint32_t*)nc_alloc_copy(o, fg.len.data(), fg.len.size() * 4);
+    nc.dev.fn_short = fg.n_short;
+    nc.dev.max_chain = t.max_chain;
+    nc.dev.W = t.W;
+    nc.flag = t.flag;
+    nc.set = true;
+    nc.build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+
+int pm_hip_pattern_nocase(void* obj, uint32_t gid) {
+    PmHip* o = as(obj);
+    return o->nc.set && gid != 0 && gid < o->nc.flag.size() ? (int)o->nc.flag[gid] : -1;
+}
+
+uint32_t pm_hip_nocase_flow_states(void* obj) { return as(obj)->nc.set ? as(obj)->nc.dfa_states : 0u; }
+
+uint32_t pm_hip_case_words(void* obj) { return as(obj)->nc.set ? as(obj)->nc.dev.W : 0u; }
+
+int pm_hip_nocase_stats(void* obj, double* build_ms, double* upload_ms, size_t* table_bytes) {
+    PmHip* o = as(obj);
+    if (!o->nc.set) return -1;
+    if (build_ms) *build_ms = o->nc.build_s * 1e3;
+    if (upload_ms) *upload_ms = o->nc.upload_s * 1e3;
+    if (table_bytes) *table_bytes = o->nc.bytes;
+    return 0;
+}
+
+int pm_hip_scan_batch_nocase_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_stream_groups, uint32_t min_len, int all,
+                                    uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                                    void* hip_stream) {
+    PmHip* o = as(obj);
+    if (const int rc = batch_check(o)) return rc;
+    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) ||
+        ((uintptr_t)d_stream_groups & 3) || (nseg > 0 && n > 0 && (!d_text || !d_offsets))) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned, stream groups 4-B "
+                      "aligned)");
+        return -2;
+    }
+    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
+    if (const int rc = events_gid_check(o)) return rc;
+    if (const int rc = nocase_check(o, false, d_stream_groups)) return rc;
+    if (nseg == 0 || n == 0) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess)
+        e = pm_launch_rt_batch_nocase(d_text, d_offsets, nseg, n, events_dev(o, min_len, d_events, cap, d_nevents),
+                                      nocase_dev(o, nullptr, nullptr),
+                                      o->d_gmask ? groups_dev(o, d_stream_groups) : GroupDev{nullptr, nullptr, nullptr},
+                                      o->d_win ? windows_dev(o, nullptr, nullptr) : WinDev{nullptr, nullptr, nullptr},
+                                      all != 0, nocase_rt(o), o->num_cu, (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "batch nocase launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_RT;
+    o->last_form = 0;
+    return 0;
+}
+
+int pm_hip_scan_flows_nocase_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
+                                    int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out,
+                                    const uint32_t* d_stream_groups, uint32_t min_len, int all, uint64_t* d_events,
+                                    uint64_t cap, unsigned long long* d_nevents, void* hip_stream,
+                                    const uint64_t* d_pos_in, uint64_t* d_pos_out, const uint64_t* d_case_in,
+                                    uint64_t* d_case_out) {
+    PmHip* o = as(obj);
+    if (const int rc = flows_check(o)) return rc;
+    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_state_in & 3) ||
+        ((uintptr_t)d_state_out & 3) || ((uintptr_t)d_stream_groups & 3) || ((uintptr_t)d_pos_in & 7) ||
+        ((uintptr_t)d_pos_out & 7) || (d_state_in && d_state_in == d_state_out) ||
+        (d_pos_in && d_pos_in == d_pos_out) || (nseg > 0 && (!d_offsets || (n > 0 && !d_text)))) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets and positions 8-B aligned, states "
+                      "and stream groups 4-B aligned, state_in != state_out, pos_in != pos_out)");
+        return -2;
+    }
+    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
+    if (const int rc = events_gid_check(o)) return rc;
+    if (const int rc = nocase_check(o, true, d_stream_groups)) return rc;
+    if (o->nc.dev.W && (((uintptr_t)d_case_in & 7) || ((uintptr_t)d_case_out & 7) ||
+                        (d_case_in && d_case_in == d_case_out))) {
+        std::snprintf(g_err, sizeof(g_err), "bad arguments (case histories 8-B aligned, case_in != case_out)");
+        return -2;
+    }
+    const bool hist = o->nc.dev.W && d_case_out;
+    const bool pos = o->d_win && d_pos_out;
+    if (nseg == 0 || (n == 0 && !d_state_out && !pos && !hist)) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess)
+        e = pm_launch_dfa_flows_nocase(
+            d_text, d_offsets, nseg, n, d_state_in, d_state_out, events_dev(o, min_len, d_events, cap, d_nevents),
+            nocase_dev(o, d_case_in, d_case_out),
+            o->d_gmask ? groups_dev(o, d_stream_groups) : GroupDev{nullptr, nullptr, nullptr},
+            o->d_win ? windows_dev(o, d_pos_in, d_pos_out) : WinDev{nullptr, nullptr, nullptr}, all != 0, nocase_dfa(o),
+            o->nc.dfa_states, o->flow_seg, o->num_cu, (hipStream_t)hip_stream);
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "flow nocase launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    o->last_kernel = KIND_AC;
+    o->last_form = 1;
+    return 0;
+}
+
+int pm_hip_read_batch_nocase(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg,
+                             const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
+                             size_t* nevents) {
+    GroupArgs ga{stream_groups, all != 0};
+    ga.nocase = true;
+    return read_events(as(obj), false, true, buf, offsets, nseg, nullptr, min_len, events, cap, nevents, &ga);
+}
+
+int pm_hip_read_flows_nocase(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
+                             uint64_t* pos, uint64_t* case_hist, const uint32_t* stream_groups, uint32_t min_len,
+                             int all, uint64_t* events, size_t cap, size_t* nevents) {
+    GroupArgs ga{stream_groups, all != 0};
+    ga.pos = pos;
+    ga.nocase = true;
+    ga.case_hist = case_hist;
+    return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents, &ga);
+}
+
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,
                         unsigned long long* d_counts, void* hip_stream) {
     PmHip* o = as(obj);
@@ -2408,6 +2703,7 @@ size_t pm_hip_scratch_bytes(void* obj) {
     if (o->batch.d_ev) b += o->batch.cap_ev * sizeof(uint64_t) + sizeof(unsigned long long);
     if (o->batch.d_grp) b += o->batch.cap_grp * sizeof(uint32_t);
     if (o->batch.d_pos_in) b += 2 * o->batch.cap_pos * sizeof(uint64_t);
+    if (o->batch.d_case_in) b += 2 * o->batch.cap_case * sizeof(uint64_t);
     return b;
 }
 
@@ -2662,6 +2958,13 @@ struct PmFlatHandle {
     bool has_fl = false;
     int kind = 0;
     bool hit = false;
+    // pm_flat_build_nocase: the folded dictionary's image of the same kind and the class tables
+    bool nocase = false;
+    PmGidMap fg;
+    RtImage frt;
+    DfaImage fdfa;
+    PmNocaseTables nc;
+    std::vector<uint32_t> ncinfo;  // pm_flat_array "nc_info"
 };
 }  // namespace
 
@@ -2723,6 +3026,19 @@ size_t pm_flat_array(void* handle, const char* name, const void** data, size_t* 
     if (s == "len") return ret(h->g.len);
     if (s == "parent") return ret(h->par.parent);
     if (s == "depth") return ret(h->par.depth);
+    if (h->nocase) {
+        if (s == "nc_head") return ret(h->nc.head);
+        if (s == "nc_cnext") return ret(h->nc.cnext);
+        if (s == "nc_cword") return ret(h->nc.cword);
+        if (s == "nc_flen") return ret(h->fg.len);
+        if (s == "nc_pool") return ret(h->nc.pool);
+        if (s == "nc_flag") return ret(h->nc.flag);
+        if (s == "nc_info") {
+            h->ncinfo = {h->nc.max_chain, h->nc.W, h->nc.lcs, (uint32_t)h->fg.index_of_gid.size() - 1, h->fg.n_short,
+                         h->kind == 2 ? h->fdfa.states : 0u};
+            return ret(h->ncinfo);
+        }
+    }
     *data = nullptr;
     *elem_size = 0;
     return 0;
@@ -2874,6 +3190,82 @@ int pm_flat_expand_windows(void* handle, const uint32_t* gids, size_t n, const i
     if (groups_by_index) gt = pm_group_tables(h->g, h->par, groups_by_index);
     pm_expand_windows(h->g, h->par, groups_by_index ? &gt : nullptr, wt, gids, n, offsets, nseg, pos_in, stream_groups,
                       min_len, all != 0, events, cap, nevents);
+    return 0;
+}
+
+// pm_flat_build_cached plus what pm_hip_set_nocase builds, from the same builders.
+void* pm_flat_build_nocase(const char* const* pats, const uint32_t* lens, const uint8_t* nocase, size_t n, int kind,
+                           const char* cache_dir) {
+    if (!nocase && n) return nullptr;
+    PmFlatHandle* h = static_cast<PmFlatHandle*>(pm_flat_build_cached(pats, lens, n, kind, cache_dir));
+    std::vector<std::string> v, fpats;
+    v.reserve(n);
+    for (size_t i = 0; i < n; ++i) v.emplace_back(pats[i], lens[i]);
+    std::vector<uint32_t> fidx;
+    pm_nocase_fold(v, fpats, fidx);
+    h->fg = pm_assign_gids(fpats);
+    bool hit = false;
+    PmImages im = pm_build_images_cached(fpats, h->fg, kind, cache_dir ? cache_dir : "", &hit);
+    h->nc = pm_nocase_tables(v, h->g, nocase, fidx, h->fg, im.par);
+    h->frt = std::move(im.rt);
+    h->fdfa = std::move(im.dfa);
+    if (!h->fdfa.next.empty()) pm_nocase_dup_rows(h->fdfa);
+    h->nocase = true;
+    return h;
+}
+
+// The nocase kernels' contract on the host: the folded automaton's dense answers (the reverse
+// walk from each stream's start over folded bytes, or the flow walk over the doubled rows), then
+// pm_expand_nocase; pm_nocase_history for the words out.
+int pm_flat_host_scan_nocase(void* handle, const uint8_t* text, const int64_t* offsets, size_t nseg,
+                             const uint32_t* state_in, uint32_t* state_out, const uint64_t* pos_in, uint64_t* pos_out,
+                             const uint64_t* case_in, uint64_t* case_out, const uint32_t* stream_groups,
+                             const uint32_t* groups_by_index, const uint32_t* min_start_by_index,
+                             const uint32_t* max_end_by_index, uint32_t min_len, int all, uint64_t* events, size_t cap,
+                             size_t* nevents) {
+    PmFlatHandle* h = static_cast<PmFlatHandle*>(handle);
+    if (!h->nocase || (h->kind == 1 && !h->frt.fits)) return -1;
+    if (min_len == 0 || !nevents || (cap && !events) || (nseg && !offsets) || (stream_groups && !groups_by_index) ||
+        !min_start_by_index != !max_end_by_index)
+        return -2;
+    for (size_t j = 0; j < nseg; ++j)
+        if (offsets[j] > offsets[j + 1] || offsets[0] != 0) return -2;
+    const size_t n = nseg ? (size_t)offsets[nseg] : 0;
+    if (n > ((size_t)1 << 40) || (n && !text)) return -2;
+    if (min_start_by_index)
+        for (size_t k = 0; k < h->g.gid_of_index.size(); ++k)
+            if (min_start_by_index[k] > 0x7FFFFFFFu) return -2;
+    if (h->par.parent.size() > ((size_t)1 << 24)) return -4;
+    const bool flows = h->kind == 2;
+    std::vector<uint32_t> fgids(n);
+    std::vector<uint32_t> st_out(nseg);
+    if (flows) {
+        if (pm_host_scan_flows(h->fdfa, text, offsets, nseg, state_in, st_out.data(), fgids.data())) return -2;
+    } else {
+        std::vector<uint8_t> ft(n);
+        for (size_t k = 0; k < n; ++k) ft[k] = pm_fold(text[k]);
+        for (size_t j = 0; j < nseg; ++j)
+            for (int64_t k = offsets[j]; k < offsets[j + 1]; ++k)
+                fgids[k] = pm_rt_host_answer(h->frt, ft.data() + k, (size_t)(k - offsets[j] + 1));
+    }
+    PmGroupTables gt;
+    PmWindowTables wt;
+    if (groups_by_index) gt = pm_group_tables(h->g, h->par, groups_by_index);
+    if (min_start_by_index) wt = pm_window_tables(h->g, h->par, min_start_by_index, max_end_by_index);
+    pm_expand_nocase(h->g, h->nc, groups_by_index ? &gt : nullptr, min_start_by_index ? &wt : nullptr, text,
+                     fgids.data(), n, offsets, nseg, flows ? pos_in : nullptr, flows ? case_in : nullptr, stream_groups,
+                     min_len, all != 0, events, cap, nevents);
+    if (flows) {
+        if (case_out && h->nc.W) {
+            std::vector<uint64_t> co(nseg * (size_t)h->nc.W);
+            pm_nocase_history(text, offsets, nseg, h->nc.W, case_in, co.data());
+            std::memcpy(case_out, co.data(), co.size() * sizeof(uint64_t));
+        }
+        if (pos_out)
+            for (size_t j = 0; j < nseg; ++j)
+                pos_out[j] = (pos_in ? pos_in[j] : 0) + (uint64_t)(offsets[j + 1] - offsets[j]);
+        if (state_out) std::memcpy(state_out, st_out.data(), nseg * sizeof(uint32_t));
+    }
     return 0;
 }
 

@@ -157,6 +157,10 @@ class FlowTable:
         self.matcher = matcher
         self.states = {}
         self.bytes = {}  # flow key -> the bytes the flow has had (scan_windows' positions)
+        # scan_nocase: the folded automaton's states, the case histories, and the bytes it saw
+        self.nocase_states = {}
+        self.nocase_case = {}
+        self.nocase_bytes = {}
 
     def scan(self, packets):
         """packets: a list of (key, bytes-like).  Returns the codes of each
@@ -222,6 +226,50 @@ class FlowTable:
             return self.matcher.read_flows_windows(data, offs, grp, state, pos_in, min_len, all_matches)[:3]
         return self._scan_list([(p[0], p[1]) for p in packets], min_len, read, "scan_windows")
 
+    def scan_nocase(self, packets, min_len=3, all_matches=True):
+        """scan_windows() with the patterns' nocase flags honoured
+        (HipMatcher.set_nocase; groups and windows where they are set):
+        packets as there.  The nocase scan walks the folded automaton, so the
+        table keeps its states and the flows' case histories in dictionaries
+        of their own, beside the bytes each flow had when scan_nocase last
+        saw it.  A flow that got bytes through another scan method since
+        cannot be continued (the folded automaton missed them): ValueError."""
+        grp = None
+        if packets and len(packets[0]) == 3:
+            grp = np.array([g for _, _, g in packets], dtype=np.uint32)
+        keys = [p[0] for p in packets]
+        if len(set(keys)) != len(keys):
+            seen = set()
+            dup = next(k for k in keys if k in seen or seen.add(k))
+            raise ValueError(f"flow {dup!r} appears twice in one scan_nocase(): concatenate its packets")
+        for k in keys:
+            if self.bytes.get(k, 0) != self.nocase_bytes.get(k, 0):
+                raise ValueError(f"flow {k!r} has had {self.bytes.get(k, 0)} bytes but scan_nocase() saw "
+                                 f"{self.nocase_bytes.get(k, 0)} of them")
+        if not packets:
+            return []
+        bufs = [p[1] for p in packets]
+        offs = batch_offsets(bufs)
+        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in bufs]
+        data = np.concatenate(parts)
+        W = self.matcher.case_words
+        state = np.array([self.nocase_states.get(k, 0) for k in keys], dtype=np.uint32)
+        pos_in = np.array([self.bytes.get(k, 0) for k in keys], dtype=np.uint64)
+        case = np.zeros((len(keys), W), dtype=np.uint64)
+        for r, k in enumerate(keys):
+            if k in self.nocase_case:
+                case[r] = self.nocase_case[k]
+        pos, codes, state, _, case = self.matcher.read_flows_nocase(data, offs, grp, state, pos_in, case, min_len,
+                                                                    all_matches)
+        for r, k in enumerate(keys):
+            self.nocase_states[k] = int(state[r])
+            self.nocase_case[k] = case[r].copy()
+        self._advance(keys, offs)
+        for k in keys:
+            self.nocase_bytes[k] = self.bytes[k]
+        return _split_events(pos, codes, offs)
+
     def _advance(self, keys, offs):
         for k, n in zip(keys, np.diff(offs).tolist()):
             self.bytes[k] = self.bytes.get(k, 0) + n
@@ -250,6 +298,9 @@ class FlowTable:
         """Forget a flow: its key, seen again, starts a fresh one."""
         self.states.pop(key, None)
         self.bytes.pop(key, None)
+        self.nocase_states.pop(key, None)
+        self.nocase_case.pop(key, None)
+        self.nocase_bytes.pop(key, None)
 
     def __len__(self):
         return len(self.states)
@@ -766,6 +817,152 @@ class HipMatcher:
         ev, st, ps = self._read_windows(data, offsets, stream_groups, st, ps, min_len, all_matches)
         p, gids = unpack_events(ev)
         return p, self._codes[gids], st, ps
+
+    # --- per-pattern nocase: case-insensitive patterns in the list scans -----
+    def set_nocase(self, flags):
+        """pm_hip_set_nocase: flags[k] != 0 makes the k-th pattern added
+        case-insensitive (ASCII).  After compile(); builds and uploads the
+        folded images; a later call rebuilds them (no nocase scan may be in
+        flight)."""
+        f = np.ascontiguousarray(np.asarray(flags) != 0, dtype=np.uint8)
+        if f.ndim != 1:
+            raise ValueError("flags: one value per pattern added")
+        rc = self.lib.pm_hip_set_nocase(self.obj, f.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), f.size)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def pattern_nocase(self, gid):
+        """The nocase flag of pattern gid (bool); None out of range or before
+        set_nocase."""
+        rc = self.lib.pm_hip_pattern_nocase(self.obj, gid)
+        return None if rc < 0 else bool(rc)
+
+    @property
+    def nocase_flow_states(self):
+        """States of the folded automaton: the nocase flow scans' states are
+        its own, below this value (0 before set_nocase or without a DFA)."""
+        return int(self.lib.pm_hip_nocase_flow_states(self.obj))
+
+    @property
+    def case_words(self):
+        """W: the u64 words of case history a flow carries through the
+        nocase flow scans (0: none needed)."""
+        return int(self.lib.pm_hip_case_words(self.obj))
+
+    def nocase_stats(self):
+        """(build ms, upload ms, table bytes) of the last set_nocase; None
+        before it."""
+        b, u, t = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_size_t(0)
+        if self.lib.pm_hip_nocase_stats(self.obj, ctypes.byref(b), ctypes.byref(u), ctypes.byref(t)) != 0:
+            return None
+        return b.value, u.value, int(t.value)
+
+    def scan_batch_nocase_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_stream_groups_ptr, min_len, all_matches,
+                                 d_events_ptr, cap, d_nevents_ptr, stream_ptr):
+        """pm_hip_scan_batch_nocase_device: scan_batch_windows_device with the
+        patterns' nocase flags honoured; group and window tables are used
+        where the object has them."""
+        rc = self.lib.pm_hip_scan_batch_nocase_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n,
+                                                      d_stream_groups_ptr, min_len, int(bool(all_matches)),
+                                                      d_events_ptr, cap, d_nevents_ptr, stream_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def scan_flows_nocase_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr,
+                                 d_stream_groups_ptr, min_len, all_matches, d_events_ptr, cap, d_nevents_ptr,
+                                 stream_ptr, d_pos_in_ptr=None, d_pos_out_ptr=None, d_case_in_ptr=None,
+                                 d_case_out_ptr=None):
+        """pm_hip_scan_flows_nocase_device: scan_flows_windows_device over the
+        folded automaton (states below nocase_flow_states) with nseg *
+        case_words u64 of case history in and out per call."""
+        rc = self.lib.pm_hip_scan_flows_nocase_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr,
+                                                      d_state_out_ptr, d_stream_groups_ptr, min_len,
+                                                      int(bool(all_matches)), d_events_ptr, cap, d_nevents_ptr,
+                                                      stream_ptr, d_pos_in_ptr, d_pos_out_ptr, d_case_in_ptr,
+                                                      d_case_out_ptr)
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
+    def _read_nocase(self, data, offsets, stream_groups, state, pos, case, min_len, all_matches):
+        """The host nocase forms: (events u64 ascending, state_out, pos_out,
+        case_out -- None for the batched form); a short host buffer means one
+        more call, as in _read_events."""
+        arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
+                                   else data, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offs.ndim != 1 or offs.size < 1 or int(offs[-1]) != len(arr):
+            raise ValueError("offsets: nseg + 1 values, the last one len(data)")
+        nseg = offs.size - 1
+        for name, a in (("state", state), ("pos", pos)):
+            if a is not None and a.shape != (nseg,):
+                raise ValueError(f"{name}: nseg values")
+        if case is not None and case.shape != (nseg, self.case_words):
+            raise ValueError("case: nseg rows of case_words values")
+        grp = None
+        if stream_groups is not None:
+            grp = np.ascontiguousarray(stream_groups, dtype=np.uint32)
+            if grp.shape != (nseg,):
+                raise ValueError("stream_groups: nseg values")
+        u32p, u64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+        cap = max(1024, len(arr) // 16)
+        while True:
+            ev = np.empty(cap, dtype=np.uint64)
+            total = ctypes.c_size_t(0)
+            st = None if state is None else state.copy()
+            ps = None if pos is None else pos.copy()
+            cs = None if case is None else case.copy()
+            head = (self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                    offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg)
+            tail = (None if grp is None else grp.ctypes.data_as(u32p), min_len, int(bool(all_matches)),
+                    ev.ctypes.data_as(u64p), cap, ctypes.byref(total))
+            if state is None:
+                rc = self.lib.pm_hip_read_batch_nocase(*head, *tail)
+            else:
+                rc = self.lib.pm_hip_read_flows_nocase(*head, st.ctypes.data_as(u32p),
+                                                       None if ps is None else ps.ctypes.data_as(u64p),
+                                                       None if cs is None or cs.size == 0 else cs.ctypes.data_as(u64p),
+                                                       *tail)
+            if rc != 0:
+                raise RuntimeError(self.lib.pm_hip_last_error().decode())
+            if total.value <= cap:
+                return ev[:total.value], st, ps, cs
+            cap = total.value
+
+    def read_batch_nocase(self, data, offsets, stream_groups=None, min_len=3, all_matches=True):
+        """pm_hip_read_batch_nocase: read_batch_windows with the patterns'
+        nocase flags honoured (groups and windows where they are set):
+        (positions int64, codes), ascending by position, then gid."""
+        ev, _, _, _ = self._read_nocase(data, offsets, stream_groups, None, None, None, min_len, all_matches)
+        pos, gids = unpack_events(ev)
+        return pos, self._codes[gids]
+
+    def read_many_nocase(self, buffers, stream_groups=None, min_len=3, all_matches=True):
+        """read_batch_nocase over a list of buffers, each a stream of its own:
+        per buffer (positions inside it, codes)."""
+        offs = batch_offsets(buffers)
+        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
+        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        pos, codes = self.read_batch_nocase(data, offs, stream_groups, min_len, all_matches)
+        return _split_events(pos, codes, offs)
+
+    def read_flows_nocase(self, data, offsets, stream_groups=None, state=None, pos=None, case=None, min_len=3,
+                          all_matches=True):
+        """pm_hip_read_flows_nocase: read_flows_windows over the folded
+        automaton.  state: the folded automaton's states (None: fresh);
+        pos: the bytes every flow had before (None: 0; used where windows are
+        set); case: (nseg, case_words) u64 of case history (None: zero).
+        Returns (positions, codes, state_out, pos_out, case_out); pos_out
+        counts the bytes whether or not windows are set."""
+        nseg = len(offsets) - 1
+        st = np.zeros(nseg, dtype=np.uint32) if state is None else np.array(state, dtype=np.uint32, order="C")
+        ps = np.zeros(nseg, dtype=np.uint64) if pos is None else np.array(pos, dtype=np.uint64, order="C")
+        cs = (np.zeros((nseg, self.case_words), dtype=np.uint64) if case is None
+              else np.array(case, dtype=np.uint64, order="C").reshape(nseg, self.case_words))
+        ev, st, ps2, cs = self._read_nocase(data, offsets, stream_groups, st, ps, cs, min_len, all_matches)
+        p, gids = unpack_events(ev)
+        ps = ps + np.diff(np.asarray(offsets, dtype=np.int64)).astype(np.uint64)
+        return p, self._codes[gids], st, ps, cs
 
     # --- flow scan: the batched layout with a carried state per stream -----
     def scan_flows_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr, d_out_ptr,
