@@ -4561,9 +4561,20 @@ hipError_t pm_launch_rt(const uint8_t* text, int64_t stream_start, int64_t pos0,
     return launch_rt_impl(false, text, stream_start, pos0, n, out, outw, count, t, num_cu, s);
 }
 
-// The batched scan (rt_batch_kernel): at most small_max positions, one
-// 1,024-position tile per workgroup over the global tables; above, one
-// workgroup per CU, each over a contiguous share of the tiles.  No scratch,
+// The grid of a batched launch of n > 0 positions, and which of its two kernel
+// forms runs: at most small_max positions (the "rt_small_max" option; below 0
+// RT_SMALL_MAX), one 1,024-position tile per workgroup; above, one workgroup
+// per CU, each over a contiguous share of the tiles.
+static dim3 batch_grid(int64_t n, int64_t small_max, int num_cu, bool& small) {
+    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
+    small = n <= (small_max >= 0 ? small_max : RT_SMALL_MAX) && ntiles <= (int64_t)1 << 30;
+    return dim3((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu));
+}
+
+// What every list launch needs of its events argument.
+static bool ev_ok(const EvDev& ev) { return ev.cursor && ev.len && ev.min_len >= 1 && (ev.events || !ev.cap); }
+
+// The batched scan (rt_batch_kernel) over the global tables.  No scratch,
 // nothing allocated: legal under stream capture.
 hipError_t pm_launch_rt_batch(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n, void* out,
                               int outw, unsigned long long* count, const RtDev& t, int num_cu, hipStream_t s) {
@@ -4571,10 +4582,8 @@ hipError_t pm_launch_rt_batch(const uint8_t* text, const int64_t* offsets, int64
     if (!text || !offsets || num_cu <= 0) return hipErrorInvalidValue;
     if (!out) outw = 0;
     if (outw != 0 && outw != 2 && outw != 4) return hipErrorInvalidValue;
-    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
-    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
-    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
-    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    bool small;
+    const dim3 g = batch_grid(n, t.small_max, num_cu, small), b(RT_THREADS);
 #define PM_BATCH_LAUNCH(W_)                                                                                         \
     do {                                                                                                            \
         if (small) hipLaunchKernelGGL((rt_batch_kernel<W_, true>), g, b, 0, s, text, offsets, nseg, n, out, count, t); \
@@ -4591,12 +4600,9 @@ hipError_t pm_launch_rt_batch(const uint8_t* text, const int64_t* offsets, int64
 hipError_t pm_launch_rt_batch_events(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
                                      const EvDev& ev, const RtDev& t, int num_cu, hipStream_t s) {
     if (n <= 0 || nseg <= 0) return hipSuccess;
-    if (!text || !offsets || num_cu <= 0) return hipErrorInvalidValue;
-    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap)) return hipErrorInvalidValue;
-    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
-    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
-    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
-    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    if (!text || !offsets || num_cu <= 0 || !ev_ok(ev)) return hipErrorInvalidValue;
+    bool small;
+    const dim3 g = batch_grid(n, t.small_max, num_cu, small), b(RT_THREADS);
     if (small) hipLaunchKernelGGL(rt_batch_events_kernel<true>, g, b, 0, s, text, offsets, nseg, n, ev, t);
     else hipLaunchKernelGGL(rt_batch_events_kernel<false>, g, b, 0, s, text, offsets, nseg, n, ev, t);
     return hipGetLastError();
@@ -4606,12 +4612,9 @@ hipError_t pm_launch_rt_batch_events(const uint8_t* text, const int64_t* offsets
 hipError_t pm_launch_rt_batch_matches(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
                                       const EvDev& ev, const MatchDev& mx, const RtDev& t, int num_cu, hipStream_t s) {
     if (n <= 0 || nseg <= 0) return hipSuccess;
-    if (!text || !offsets || num_cu <= 0) return hipErrorInvalidValue;
-    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent) return hipErrorInvalidValue;
-    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
-    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
-    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
-    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    if (!text || !offsets || num_cu <= 0 || !ev_ok(ev) || !mx.parent) return hipErrorInvalidValue;
+    bool small;
+    const dim3 g = batch_grid(n, t.small_max, num_cu, small), b(RT_THREADS);
     if (small) hipLaunchKernelGGL(rt_batch_matches_kernel<true>, g, b, 0, s, text, offsets, nseg, n, ev, mx, t);
     else hipLaunchKernelGGL(rt_batch_matches_kernel<false>, g, b, 0, s, text, offsets, nseg, n, ev, mx, t);
     return hipGetLastError();
@@ -4622,13 +4625,10 @@ hipError_t pm_launch_rt_batch_groups(const uint8_t* text, const int64_t* offsets
                                      const EvDev& ev, const MatchDev& mx, const GroupDev& gr, bool all,
                                      const RtDev& t, int num_cu, hipStream_t s) {
     if (n <= 0 || nseg <= 0) return hipSuccess;
-    if (!text || !offsets || num_cu <= 0) return hipErrorInvalidValue;
-    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent || !gr.gmask || !gr.reach)
+    if (!text || !offsets || num_cu <= 0 || !ev_ok(ev) || !mx.parent || !gr.gmask || !gr.reach)
         return hipErrorInvalidValue;
-    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
-    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
-    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
-    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    bool small;
+    const dim3 g = batch_grid(n, t.small_max, num_cu, small), b(RT_THREADS);
     auto* const k = small ? (all ? rt_batch_groups_kernel<true, true> : rt_batch_groups_kernel<true, false>)
                           : (all ? rt_batch_groups_kernel<false, true> : rt_batch_groups_kernel<false, false>);
     hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, ev, mx, gr, t);
@@ -4641,14 +4641,11 @@ hipError_t pm_launch_rt_batch_windows(const uint8_t* text, const int64_t* offset
                                       const EvDev& ev, const MatchDev& mx, const GroupDev& gr, const WinDev& wn,
                                       bool all, const RtDev& t, int num_cu, hipStream_t s) {
     if (n <= 0 || nseg <= 0) return hipSuccess;
-    if (!text || !offsets || num_cu <= 0) return hipErrorInvalidValue;
-    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent || !wn.win ||
-        !gr.gmask != !gr.reach || (!gr.gmask && gr.stream_groups))
+    if (!text || !offsets || num_cu <= 0 || !ev_ok(ev) || !mx.parent || !wn.win || !gr.gmask != !gr.reach ||
+        (!gr.gmask && gr.stream_groups))
         return hipErrorInvalidValue;
-    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
-    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
-    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
-    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    bool small;
+    const dim3 g = batch_grid(n, t.small_max, num_cu, small), b(RT_THREADS);
     auto* const k = small ? (all ? rt_batch_windows_kernel<true, true> : rt_batch_windows_kernel<true, false>)
                           : (all ? rt_batch_windows_kernel<false, true> : rt_batch_windows_kernel<false, false>);
     hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, ev, mx, gr, wn, t);
@@ -4886,25 +4883,36 @@ hipError_t pm_launch_dfa_flows(const uint8_t* text, const int64_t* offsets, int6
     return hipGetLastError();
 }
 
-// The flow scan's events form (dfa_flow_events_kernel): the count-only
-// launch's segments (no id stores to align to lines).
+// What the flow list launches share once a form has found something to do: the pointers and the
+// image every one of them reads, the "flow_seg" option's range, the count-only launch's segments
+// and grid (no id stores to align to lines), and the 3-gram table where "dfa_sync" is on.
+struct FlowLaunch {
+    int64_t seg;
+    dim3 g;
+    const uint32_t* g3;
+};
+static bool flow_list_launch(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n, const DfaDev& t,
+                             uint32_t states, int64_t force_seg, int num_cu, FlowLaunch& f) {
+    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return false;
+    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return false;
+    int64_t blocks;
+    if (!flow_shape(nseg, n, 16, force_seg, num_cu, f.seg, blocks)) return false;
+    f.g = dim3((unsigned)blocks);
+    f.g3 = t.sync ? t.gram3 : nullptr;
+    return true;
+}
+
+// The flow scan's events form (dfa_flow_events_kernel).
 hipError_t pm_launch_dfa_flows_events(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
                                       const uint32_t* state_in, uint32_t* state_out, const EvDev& ev,
                                       const DfaDev& t, uint32_t states, int64_t force_seg, int num_cu, hipStream_t s) {
     if (nseg <= 0 || n < 0 || (n == 0 && !state_out)) return hipSuccess;
-    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
-    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap)) return hipErrorInvalidValue;
-    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
-    int64_t seg, blocks;
-    if (!flow_shape(nseg, n, 16, force_seg, num_cu, seg, blocks)) return hipErrorInvalidValue;
-    const dim3 g((unsigned)blocks), b(DFA_THREADS);
-    const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
-    if (t.coded)
-        hipLaunchKernelGGL(dfa_flow_events_kernel<true>, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev,
-                           t.next, t.out, states, t.warm, seg, g3);
-    else
-        hipLaunchKernelGGL(dfa_flow_events_kernel<false>, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev,
-                           t.next, t.out, states, t.warm, seg, g3);
+    if (!ev_ok(ev)) return hipErrorInvalidValue;
+    FlowLaunch f;
+    if (!flow_list_launch(text, offsets, nseg, n, t, states, force_seg, num_cu, f)) return hipErrorInvalidValue;
+    auto* const k = t.coded ? dfa_flow_events_kernel<true> : dfa_flow_events_kernel<false>;
+    hipLaunchKernelGGL(k, f.g, dim3(DFA_THREADS), 0, s, text, offsets, nseg, n, state_in, state_out, ev, t.next, t.out,
+                       states, t.warm, f.seg, f.g3);
     return hipGetLastError();
 }
 
@@ -4914,19 +4922,12 @@ hipError_t pm_launch_dfa_flows_matches(const uint8_t* text, const int64_t* offse
                                        const MatchDev& mx, const DfaDev& t, uint32_t states, int64_t force_seg,
                                        int num_cu, hipStream_t s) {
     if (nseg <= 0 || n < 0 || (n == 0 && !state_out)) return hipSuccess;
-    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
-    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent) return hipErrorInvalidValue;
-    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
-    int64_t seg, blocks;
-    if (!flow_shape(nseg, n, 16, force_seg, num_cu, seg, blocks)) return hipErrorInvalidValue;
-    const dim3 g((unsigned)blocks), b(DFA_THREADS);
-    const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
-    if (t.coded)
-        hipLaunchKernelGGL(dfa_flow_matches_kernel<true>, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev,
-                           mx, t.next, t.out, states, t.warm, seg, g3);
-    else
-        hipLaunchKernelGGL(dfa_flow_matches_kernel<false>, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev,
-                           mx, t.next, t.out, states, t.warm, seg, g3);
+    if (!ev_ok(ev) || !mx.parent) return hipErrorInvalidValue;
+    FlowLaunch f;
+    if (!flow_list_launch(text, offsets, nseg, n, t, states, force_seg, num_cu, f)) return hipErrorInvalidValue;
+    auto* const k = t.coded ? dfa_flow_matches_kernel<true> : dfa_flow_matches_kernel<false>;
+    hipLaunchKernelGGL(k, f.g, dim3(DFA_THREADS), 0, s, text, offsets, nseg, n, state_in, state_out, ev, mx, t.next, t.out,
+                       states, t.warm, f.seg, f.g3);
     return hipGetLastError();
 }
 
@@ -4936,18 +4937,13 @@ hipError_t pm_launch_dfa_flows_groups(const uint8_t* text, const int64_t* offset
                                       const MatchDev& mx, const GroupDev& gr, bool all, const DfaDev& t,
                                       uint32_t states, int64_t force_seg, int num_cu, hipStream_t s) {
     if (nseg <= 0 || n < 0 || (n == 0 && !state_out)) return hipSuccess;
-    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
-    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent || !gr.gmask || !gr.reach)
-        return hipErrorInvalidValue;
-    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
-    int64_t seg, blocks;
-    if (!flow_shape(nseg, n, 16, force_seg, num_cu, seg, blocks)) return hipErrorInvalidValue;
-    const dim3 g((unsigned)blocks), b(DFA_THREADS);
-    const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
+    if (!ev_ok(ev) || !mx.parent || !gr.gmask || !gr.reach) return hipErrorInvalidValue;
+    FlowLaunch f;
+    if (!flow_list_launch(text, offsets, nseg, n, t, states, force_seg, num_cu, f)) return hipErrorInvalidValue;
     auto* const k = t.coded ? (all ? dfa_flow_groups_kernel<true, true> : dfa_flow_groups_kernel<true, false>)
                             : (all ? dfa_flow_groups_kernel<false, true> : dfa_flow_groups_kernel<false, false>);
-    hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev, mx, gr, t.next, t.out, states,
-                       t.warm, seg, g3);
+    hipLaunchKernelGGL(k, f.g, dim3(DFA_THREADS), 0, s, text, offsets, nseg, n, state_in, state_out, ev, mx, gr,
+                       t.next, t.out, states, t.warm, f.seg, f.g3);
     return hipGetLastError();
 }
 
@@ -4959,27 +4955,21 @@ hipError_t pm_launch_dfa_flows_windows(const uint8_t* text, const int64_t* offse
                                        const DfaDev& t, uint32_t states, int64_t force_seg, int num_cu,
                                        hipStream_t s) {
     if (nseg <= 0 || n < 0 || (n == 0 && !state_out && !wn.pos_out)) return hipSuccess;
-    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
-    if (!ev.cursor || !ev.len || ev.min_len < 1 || (!ev.events && ev.cap) || !mx.parent || !wn.win ||
-        !gr.gmask != !gr.reach || (!gr.gmask && gr.stream_groups))
+    if (!ev_ok(ev) || !mx.parent || !wn.win || !gr.gmask != !gr.reach || (!gr.gmask && gr.stream_groups))
         return hipErrorInvalidValue;
-    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
-    int64_t seg, blocks;
-    if (!flow_shape(nseg, n, 16, force_seg, num_cu, seg, blocks)) return hipErrorInvalidValue;
-    const dim3 g((unsigned)blocks), b(DFA_THREADS);
-    const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
+    FlowLaunch f;
+    if (!flow_list_launch(text, offsets, nseg, n, t, states, force_seg, num_cu, f)) return hipErrorInvalidValue;
     auto* const k = t.coded ? (all ? dfa_flow_windows_kernel<true, true> : dfa_flow_windows_kernel<true, false>)
                             : (all ? dfa_flow_windows_kernel<false, true> : dfa_flow_windows_kernel<false, false>);
-    hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev, mx, gr, wn, t.next, t.out,
-                       states, t.warm, seg, g3);
+    hipLaunchKernelGGL(k, f.g, dim3(DFA_THREADS), 0, s, text, offsets, nseg, n, state_in, state_out, ev, mx, gr, wn,
+                       t.next, t.out, states, t.warm, f.seg, f.g3);
     return hipGetLastError();
 }
 
 // The nocase forms (rt_batch_nocase_kernel, dfa_flow_nocase_kernel): the window launches over the
 // folded images.  Group and window tables are optional; stream masks only with group tables.
 static bool nocase_args_ok(const EvDev& ev, const NcDev& nc, const GroupDev& gr) {
-    return ev.cursor && ev.len && ev.min_len >= 1 && (ev.events || !ev.cap) && nc.head && nc.cnext && nc.cword &&
-           nc.pool && nc.flen && (gr.gmask || !gr.stream_groups);
+    return ev_ok(ev) && nc.head && nc.cnext && nc.cword && nc.pool && nc.flen && (gr.gmask || !gr.stream_groups);
 }
 
 hipError_t pm_launch_rt_batch_nocase(const uint8_t* text, const int64_t* offsets, int64_t nseg, int64_t n,
@@ -4987,10 +4977,8 @@ hipError_t pm_launch_rt_batch_nocase(const uint8_t* text, const int64_t* offsets
                                      const RtDev& t, int num_cu, hipStream_t s) {
     if (n <= 0 || nseg <= 0) return hipSuccess;
     if (!text || !offsets || num_cu <= 0 || !nocase_args_ok(ev, nc, gr)) return hipErrorInvalidValue;
-    const int64_t ntiles = (n + RT_BATCH_TILE - 1) / RT_BATCH_TILE;
-    const int64_t small_max = t.small_max >= 0 ? t.small_max : RT_SMALL_MAX;
-    const bool small = n <= small_max && ntiles <= (int64_t)1 << 30;
-    const dim3 g((unsigned)(small ? ntiles : ntiles < num_cu ? ntiles : num_cu)), b(RT_THREADS);
+    bool small;
+    const dim3 g = batch_grid(n, t.small_max, num_cu, small), b(RT_THREADS);
     auto* const k = small ? (all ? rt_batch_nocase_kernel<true, true> : rt_batch_nocase_kernel<true, false>)
                           : (all ? rt_batch_nocase_kernel<false, true> : rt_batch_nocase_kernel<false, false>);
     hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, ev, nc, gr, wn, t);
@@ -5004,18 +4992,14 @@ hipError_t pm_launch_dfa_flows_nocase(const uint8_t* text, const int64_t* offset
     const bool hist = nc.W && nc.case_out;
     const bool pos = wn.win && wn.pos_out;
     if (nseg <= 0 || n < 0 || (n == 0 && !state_out && !pos && !hist)) return hipSuccess;
-    if (!offsets || (n > 0 && !text) || !t.next || !t.out || states == 0 || num_cu <= 0) return hipErrorInvalidValue;
     if (!nocase_args_ok(ev, nc, gr)) return hipErrorInvalidValue;
-    if (force_seg && (force_seg < 16 || force_seg > 4096 || force_seg % 16)) return hipErrorInvalidValue;
+    FlowLaunch f;
+    if (!flow_list_launch(text, offsets, nseg, n, t, states, force_seg, num_cu, f)) return hipErrorInvalidValue;
     if (n > 0 || state_out || pos) {
-        int64_t seg, blocks;
-        if (!flow_shape(nseg, n, 16, force_seg, num_cu, seg, blocks)) return hipErrorInvalidValue;
-        const dim3 g((unsigned)blocks), b(DFA_THREADS);
-        const uint32_t* g3 = t.sync ? t.gram3 : nullptr;
         auto* const k = t.coded ? (all ? dfa_flow_nocase_kernel<true, true> : dfa_flow_nocase_kernel<true, false>)
                                 : (all ? dfa_flow_nocase_kernel<false, true> : dfa_flow_nocase_kernel<false, false>);
-        hipLaunchKernelGGL(k, g, b, 0, s, text, offsets, nseg, n, state_in, state_out, ev, nc, gr, wn, t.next, t.out,
-                           states, t.warm, seg, g3);
+        hipLaunchKernelGGL(k, f.g, dim3(DFA_THREADS), 0, s, text, offsets, nseg, n, state_in, state_out, ev, nc, gr, wn,
+                           t.next, t.out, states, t.warm, f.seg, f.g3);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -1594,6 +1594,21 @@ static void batch_stage_grow(BatchStage& q, size_t n, size_t nseg) {
     }
 }
 
+// A staging array in and its twin out (out null: an array with one side), grown
+// to the largest call so far: n elements of elem bytes each, cap of them held.
+static void stage_grow(void** in, void** out, size_t elem, size_t& cap, size_t n) {
+    if (n <= cap) return;
+    if (*in) PM_CHECK(hipFree(*in));
+    if (out && *out) PM_CHECK(hipFree(*out));
+    *in = nullptr;
+    if (out) *out = nullptr;
+    cap = 0;
+    const size_t c = std::max(n, (size_t)1 << 10);
+    PM_CHECK(hipMalloc(in, c * elem));
+    if (out) PM_CHECK(hipMalloc(out, c * elem));
+    cap = c;
+}
+
 // The host forms: text and offsets to the object's staging, one batch launch,
 // the ids back, one synchronize.  Nothing read_block / read_char carry (the
 // history, the host step's state, the picks) is read or written.
@@ -1743,16 +1758,7 @@ static int read_flows(PmHip* o, const uint8_t* buf, const int64_t* offsets, size
     PM_CHECK(hipSetDevice(o->device));
     BatchStage& q = o->batch;
     batch_stage_grow(q, n, nseg);
-    if (state && nseg > q.cap_st) {
-        if (q.d_st_in) PM_CHECK(hipFree(q.d_st_in));
-        if (q.d_st_out) PM_CHECK(hipFree(q.d_st_out));
-        q.d_st_in = q.d_st_out = nullptr;
-        q.cap_st = 0;
-        const size_t cap = std::max(nseg, (size_t)1 << 10);
-        PM_CHECK(hipMalloc(&q.d_st_in, cap * sizeof(uint32_t)));
-        PM_CHECK(hipMalloc(&q.d_st_out, cap * sizeof(uint32_t)));
-        q.cap_st = cap;
-    }
+    if (state) stage_grow((void**)&q.d_st_in, (void**)&q.d_st_out, sizeof(uint32_t), q.cap_st, nseg);
     serve_stop(o);  // a device launch wants the whole device
     PM_CHECK(hipMemcpyAsync(q.d_text, buf, n, hipMemcpyHostToDevice, q.s));
     PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
@@ -1799,14 +1805,11 @@ int pm_hip_read_flows(void* obj, const char* buf, const int64_t* offsets, size_t
 constexpr int PM_EVENT_GID_BITS = 24;  // event = position << 24 | gid
 constexpr int64_t PM_EVENT_MAX_N = (int64_t)1 << 40;
 
-// What the events forms add to their dense siblings' arguments: 0, or -2.
-static int events_args_check(int64_t n, uint32_t min_len, const uint64_t* events, uint64_t cap, const void* nevents,
-                             bool device) {
-    if (n > PM_EVENT_MAX_N || min_len < 1 || !nevents || (!events && cap) ||
-        (device && (((uintptr_t)events & 7) || ((uintptr_t)nevents & 7)))) {
+// What the list forms add to their dense siblings' arguments: 0, or -2.
+static int events_args_check(int64_t n, uint32_t min_len, const uint64_t* events, uint64_t cap, const void* nevents) {
+    if (n > PM_EVENT_MAX_N || min_len < 1 || !nevents || (!events && cap)) {
         std::snprintf(g_err, sizeof(g_err),
-                      "bad arguments (n <= 2^40, min_len >= 1, nevents required, events 8-B aligned and NULL only with "
-                      "cap == 0)");
+                      "bad arguments (n <= 2^40, min_len >= 1, nevents required, events NULL only with cap == 0)");
         return -2;
     }
     return 0;
@@ -1841,20 +1844,20 @@ static GroupDev groups_dev(PmHip* o, const uint32_t* d_stream_groups) {
     return GroupDev{o->d_gmask, o->d_reach, d_stream_groups};
 }
 
-// What the host group forms add to read_events: the streams' masks (host,
-// nseg of them; null = every stream 0xFFFFFFFF) and the form.
-struct GroupArgs {
-    const uint32_t* stream_groups;
-    bool all;
-    // the window forms (pm_hip_read_*_windows): the window kernels, and for flows the
-    // byte counts (host, nseg of them; null = all zero, nothing returned)
-    bool windows = false;
-    uint64_t* pos = nullptr;
-    // the nocase forms (pm_hip_read_*_nocase): the nocase kernels, the group and window tables
-    // where the object has them, and for flows the case histories (host, nseg * W words; null =
-    // all zero, nothing returned)
-    bool nocase = false;
-    uint64_t* case_hist = nullptr;
+// One list call: which kernels run, and the optional arrays its form has beside the text, offsets,
+// states and list every form takes.  A form leaves what it does not have null.  The device entry
+// points fill in device pointers; the host forms host ones, which read_events stages (a host form's
+// in and out are the one array the caller passed).
+enum ListForm { LIST_EVENTS, LIST_MATCHES, LIST_GROUPS, LIST_WINDOWS, LIST_NOCASE };
+static const char* const LIST_FORM_NAME[] = {"events", "matches", "groups", "windows", "nocase"};
+struct ListCall {
+    ListForm form;
+    bool all;  // an event for every pattern ending at a position, not only the longest
+    const uint32_t* stream_groups = nullptr;  // groups, windows, nocase: nseg masks; null = every stream 0xFFFFFFFF
+    const uint64_t* pos_in = nullptr;         // flows windows and nocase: nseg byte counts; null = all zero
+    uint64_t* pos_out = nullptr;              // null = not wanted
+    const uint64_t* case_in = nullptr;        // flows nocase: nseg * W words of case history; null = all zero
+    uint64_t* case_out = nullptr;             // null = not wanted
 };
 
 // -8 before pm_hip_set_windows; -7 where stream masks come without group tables.
@@ -1912,99 +1915,133 @@ static DfaDev nocase_dfa(PmHip* o) {
     return t;
 }
 
-// The batched events call; all: an event for every pattern ending at a
-// position (pm_hip_scan_batch_matches_device), not only the longest.
-static int scan_batch_events(PmHip* o, bool all, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
-                             int64_t n, uint32_t min_len, uint64_t* d_events, uint64_t cap,
-                             unsigned long long* d_nevents, void* hip_stream) {
-    if (const int rc = batch_check(o)) return rc;
-    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) ||
-        (nseg > 0 && n > 0 && (!d_text || !d_offsets))) {
-        std::snprintf(g_err, sizeof(g_err), "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned)");
+// The form's own check, once the arguments every form has are through.
+static int list_form_check(PmHip* o, bool flows, const ListCall& c) {
+    switch (c.form) {
+    case LIST_GROUPS: return groups_check(o);
+    case LIST_WINDOWS: return windows_check(o, c.stream_groups);
+    case LIST_NOCASE: return nocase_check(o, flows, c.stream_groups);
+    default: return 0;
+    }
+}
+
+// The launch of a checked list call whose arrays are all on the device: the form's tables, the
+// images it walks (the folded ones for nocase, with their own state count) and its launcher.
+// Tables the object does not hold are null, and with them the arrays only they give a meaning.
+static hipError_t list_launch(PmHip* o, bool flows, const ListCall& c, const uint8_t* d_text,
+                              const int64_t* d_offsets, int64_t nseg, int64_t n, const uint32_t* d_state_in,
+                              uint32_t* d_state_out, const EvDev& ev, hipStream_t s) {
+    const MatchDev mx = matches_dev(o);
+    const GroupDev gr = groups_dev(o, c.stream_groups);
+    const WinDev wn = o->d_win ? windows_dev(o, c.pos_in, c.pos_out) : WinDev{nullptr, nullptr, nullptr};
+    const int64_t seg = o->flow_seg;
+    const int cu = o->num_cu;
+    switch (c.form) {
+    case LIST_EVENTS:
+        return flows ? pm_launch_dfa_flows_events(d_text, d_offsets, nseg, n, d_state_in, d_state_out, ev, o->dfa,
+                                                  o->dfa_states, seg, cu, s)
+                     : pm_launch_rt_batch_events(d_text, d_offsets, nseg, n, ev, o->rt, cu, s);
+    case LIST_MATCHES:
+        return flows ? pm_launch_dfa_flows_matches(d_text, d_offsets, nseg, n, d_state_in, d_state_out, ev, mx, o->dfa,
+                                                   o->dfa_states, seg, cu, s)
+                     : pm_launch_rt_batch_matches(d_text, d_offsets, nseg, n, ev, mx, o->rt, cu, s);
+    case LIST_GROUPS:
+        return flows ? pm_launch_dfa_flows_groups(d_text, d_offsets, nseg, n, d_state_in, d_state_out, ev, mx, gr,
+                                                  c.all, o->dfa, o->dfa_states, seg, cu, s)
+                     : pm_launch_rt_batch_groups(d_text, d_offsets, nseg, n, ev, mx, gr, c.all, o->rt, cu, s);
+    case LIST_WINDOWS:
+        return flows ? pm_launch_dfa_flows_windows(d_text, d_offsets, nseg, n, d_state_in, d_state_out, ev, mx, gr, wn,
+                                                   c.all, o->dfa, o->dfa_states, seg, cu, s)
+                     : pm_launch_rt_batch_windows(d_text, d_offsets, nseg, n, ev, mx, gr, wn, c.all, o->rt, cu, s);
+    case LIST_NOCASE: {
+        const NcDev nc = nocase_dev(o, c.case_in, c.case_out);
+        return flows ? pm_launch_dfa_flows_nocase(d_text, d_offsets, nseg, n, d_state_in, d_state_out, ev, nc, gr, wn,
+                                                  c.all, nocase_dfa(o), o->nc.dfa_states, seg, cu, s)
+                     : pm_launch_rt_batch_nocase(d_text, d_offsets, nseg, n, ev, nc, gr, wn, c.all, nocase_rt(o), cu, s);
+    }
+    }
+    return hipErrorInvalidValue;
+}
+
+static bool misaligned(const void* p, uintptr_t align) { return ((uintptr_t)p & (align - 1)) != 0; }
+
+// The ten device list calls (pm_hip_scan_{batch,flows}_{events,matches,groups,windows,nocase}_device):
+// every check, in the order the return codes document, then the launch.  Nothing is written before
+// all of them pass.  A form's missing arrays are null, which passes the tests on them; the batched
+// forms have no states.
+static int scan_list_device(PmHip* o, bool flows, const ListCall& c, const uint8_t* d_text, const int64_t* d_offsets,
+                            int64_t nseg, int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out,
+                            uint32_t min_len, uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
+                            void* hip_stream) {
+    if (const int rc = flows ? flows_check(o) : batch_check(o)) return rc;
+    // (the flows' empty streams still hand their state on, so they need the offsets with n == 0 too)
+    const bool missing = flows ? nseg > 0 && (!d_offsets || (n > 0 && !d_text))
+                               : nseg > 0 && n > 0 && (!d_text || !d_offsets);
+    if (nseg < 0 || n < 0 || missing || misaligned(d_text, 16) || misaligned(d_offsets, 8) ||
+        misaligned(d_events, 8) || misaligned(d_nevents, 8) || misaligned(d_state_in, 4) ||
+        misaligned(d_state_out, 4) || misaligned(c.stream_groups, 4) || misaligned(c.pos_in, 8) ||
+        misaligned(c.pos_out, 8) || (d_state_in && d_state_in == d_state_out) || (c.pos_in && c.pos_in == c.pos_out)) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets, events, nevents and positions "
+                      "8-B aligned, states and stream groups 4-B aligned, state_in != state_out, pos_in != pos_out)");
         return -2;
     }
-    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
+    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents)) return rc;
     if (const int rc = events_gid_check(o)) return rc;
-    if (nseg == 0 || n == 0) return 0;
+    if (const int rc = list_form_check(o, flows, c)) return rc;
+    // (only now is W known; where it is 0 the histories are not read at all)
+    const uint32_t W = c.form == LIST_NOCASE ? o->nc.dev.W : 0;
+    if (W && (misaligned(c.case_in, 8) || misaligned(c.case_out, 8) || (c.case_in && c.case_in == c.case_out))) {
+        std::snprintf(g_err, sizeof(g_err), "bad arguments (case histories 8-B aligned, case_in != case_out)");
+        return -2;
+    }
+    // n == 0: the flows' copy pass still runs for whatever leaves the call -- states, positions
+    // (counted only with a window table), case histories
+    const bool carry = flows && (d_state_out || (o->d_win && c.pos_out) || (W && c.case_out));
+    if (nseg == 0 || (n == 0 && !carry)) return 0;
     hipError_t e = hipSetDevice(o->device);
     serve_stop(o);  // a device launch wants the whole device
-    if (e == hipSuccess) {
-        const EvDev ev = events_dev(o, min_len, d_events, cap, d_nevents);
-        e = all ? pm_launch_rt_batch_matches(d_text, d_offsets, nseg, n, ev, matches_dev(o), o->rt, o->num_cu,
-                                             (hipStream_t)hip_stream)
-                : pm_launch_rt_batch_events(d_text, d_offsets, nseg, n, ev, o->rt, o->num_cu, (hipStream_t)hip_stream);
-    }
+    if (e == hipSuccess)
+        e = list_launch(o, flows, c, d_text, d_offsets, nseg, n, d_state_in, d_state_out,
+                        events_dev(o, min_len, d_events, cap, d_nevents), (hipStream_t)hip_stream);
     if (e != hipSuccess) {
-        std::snprintf(g_err, sizeof(g_err), "batch %s launch: %s", all ? "matches" : "events", hipGetErrorString(e));
+        std::snprintf(g_err, sizeof(g_err), "%s %s launch: %s", flows ? "flow" : "batch", LIST_FORM_NAME[c.form],
+                      hipGetErrorString(e));
         return -3;
     }
-    o->last_kernel = KIND_RT;
-    o->last_form = 0;
+    o->last_kernel = flows ? KIND_AC : KIND_RT;
+    o->last_form = flows ? 1 : 0;
     return 0;
 }
 
 int pm_hip_scan_batch_events_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
                                     int64_t n, uint32_t min_len, uint64_t* d_events, uint64_t cap,
                                     unsigned long long* d_nevents, void* hip_stream) {
-    return scan_batch_events(as(obj), false, d_text, d_offsets, nseg, n, min_len, d_events, cap, d_nevents,
-                             hip_stream);
+    return scan_list_device(as(obj), false, ListCall{LIST_EVENTS, false}, d_text, d_offsets, nseg, n, nullptr, nullptr,
+                            min_len, d_events, cap, d_nevents, hip_stream);
 }
 
 int pm_hip_scan_batch_matches_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
                                      int64_t n, uint32_t min_len, uint64_t* d_events, uint64_t cap,
                                      unsigned long long* d_nevents, void* hip_stream) {
-    return scan_batch_events(as(obj), true, d_text, d_offsets, nseg, n, min_len, d_events, cap, d_nevents,
-                             hip_stream);
-}
-
-// The flow events call; all as in scan_batch_events.
-static int scan_flows_events(PmHip* o, bool all, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
-                             int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t min_len,
-                             uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents, void* hip_stream) {
-    if (const int rc = flows_check(o)) return rc;
-    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_state_in & 3) ||
-        ((uintptr_t)d_state_out & 3) || (d_state_in && d_state_in == d_state_out) ||
-        (nseg > 0 && (!d_offsets || (n > 0 && !d_text)))) {
-        std::snprintf(g_err, sizeof(g_err),
-                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned, states 4-B aligned, "
-                      "state_in != state_out)");
-        return -2;
-    }
-    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
-    if (const int rc = events_gid_check(o)) return rc;
-    if (nseg == 0 || (n == 0 && !d_state_out)) return 0;
-    hipError_t e = hipSetDevice(o->device);
-    serve_stop(o);  // a device launch wants the whole device
-    if (e == hipSuccess) {
-        const EvDev ev = events_dev(o, min_len, d_events, cap, d_nevents);
-        e = all ? pm_launch_dfa_flows_matches(d_text, d_offsets, nseg, n, d_state_in, d_state_out, ev, matches_dev(o),
-                                              o->dfa, o->dfa_states, o->flow_seg, o->num_cu, (hipStream_t)hip_stream)
-                : pm_launch_dfa_flows_events(d_text, d_offsets, nseg, n, d_state_in, d_state_out, ev, o->dfa,
-                                             o->dfa_states, o->flow_seg, o->num_cu, (hipStream_t)hip_stream);
-    }
-    if (e != hipSuccess) {
-        std::snprintf(g_err, sizeof(g_err), "flow %s launch: %s", all ? "matches" : "events", hipGetErrorString(e));
-        return -3;
-    }
-    o->last_kernel = KIND_AC;
-    o->last_form = 1;
-    return 0;
+    return scan_list_device(as(obj), false, ListCall{LIST_MATCHES, true}, d_text, d_offsets, nseg, n, nullptr, nullptr,
+                            min_len, d_events, cap, d_nevents, hip_stream);
 }
 
 int pm_hip_scan_flows_events_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
                                     int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t min_len,
                                     uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
                                     void* hip_stream) {
-    return scan_flows_events(as(obj), false, d_text, d_offsets, nseg, n, d_state_in, d_state_out, min_len, d_events,
-                             cap, d_nevents, hip_stream);
+    return scan_list_device(as(obj), true, ListCall{LIST_EVENTS, false}, d_text, d_offsets, nseg, n, d_state_in,
+                            d_state_out, min_len, d_events, cap, d_nevents, hip_stream);
 }
 
 int pm_hip_scan_flows_matches_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
                                      int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out, uint32_t min_len,
                                      uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
                                      void* hip_stream) {
-    return scan_flows_events(as(obj), true, d_text, d_offsets, nseg, n, d_state_in, d_state_out, min_len, d_events,
-                             cap, d_nevents, hip_stream);
+    return scan_list_device(as(obj), true, ListCall{LIST_MATCHES, true}, d_text, d_offsets, nseg, n, d_state_in,
+                            d_state_out, min_len, d_events, cap, d_nevents, hip_stream);
 }
 
 uint32_t pm_hip_pattern_len(void* obj, uint32_t gid) {
@@ -2012,20 +2049,18 @@ uint32_t pm_hip_pattern_len(void* obj, uint32_t gid) {
     return gid < o->gids.len.size() ? o->gids.len[gid] : 0u;
 }
 
-// The host forms: text, offsets (and states) to the batch staging, an events
+// The host forms: text, offsets (and states) to the batch staging, a list
 // launch into the staging's list, the count back; a list that did not hold
 // every event is grown to the count and the launch repeated from the same
 // inputs (the states come in through d_st_in and leave through d_st_out, so
 // the first launch changed nothing the second reads).  Then only the events
 // come back, are sorted, and the first min(cap, total) handed over.
 // Everything is checked before anything is written.
-// ga (the group forms, pm_hip_read_*_groups): the streams' masks are staged
-// beside the offsets and the group kernels launched; `all` is then ga->all.
-// ga->windows (pm_hip_read_*_windows): the window kernels, and the flows'
-// byte counts staged and written back like the states.
-static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
-                       uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents,
-                       const GroupArgs* ga = nullptr) {
+// c's arrays are the caller's host ones: the streams' masks, the flows' byte
+// counts and case histories are staged beside the offsets, and the latter two
+// written back like the states.
+static int read_events(PmHip* o, bool flows, const ListCall& c, const uint8_t* buf, const int64_t* offsets, size_t nseg,
+                       uint32_t* state, uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents) {
     if (const int rc = flows ? flows_check(o) : batch_check(o)) return rc;
     bool ok = (nseg == 0 || offsets) && nseg < ((size_t)1 << 60);
     if (ok && nseg) {
@@ -2034,7 +2069,7 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
         if (ok && offsets[nseg] > 0) ok = buf != nullptr;
         if (ok && flows && state)
             for (size_t j = 0; ok && j < nseg; ++j)
-                ok = state[j] < (ga && ga->nocase && o->nc.set ? o->nc.dfa_states : o->dfa_states);
+                ok = state[j] < (c.form == LIST_NOCASE && o->nc.set ? o->nc.dfa_states : o->dfa_states);
     }
     if (!ok) {
         std::snprintf(g_err, sizeof(g_err), "bad arguments (offsets[0] == 0, offsets non-decreasing%s)",
@@ -2043,71 +2078,38 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
     }
     const size_t n = nseg ? (size_t)offsets[nseg] : 0;
     if (const int rc = events_args_check((int64_t)std::min<size_t>(n, (size_t)PM_EVENT_MAX_N + 1), min_len, events, cap,
-                                         nevents, false))
+                                         nevents))
         return rc;
     if (const int rc = events_gid_check(o)) return rc;
-    if (ga)
-        if (const int rc = ga->nocase    ? nocase_check(o, flows, ga->stream_groups)
-                           : ga->windows ? windows_check(o, ga->stream_groups)
-                                         : groups_check(o))
-            return rc;
+    if (const int rc = list_form_check(o, flows, c)) return rc;
     *nevents = 0;
     if (n == 0) return 0;  // the flow form: every stream keeps its state, which the caller's array holds
     PM_CHECK(hipSetDevice(o->device));
     BatchStage& q = o->batch;
     batch_stage_grow(q, n, nseg);
     const bool st = flows && state;
-    if (st && nseg > q.cap_st) {
-        if (q.d_st_in) PM_CHECK(hipFree(q.d_st_in));
-        if (q.d_st_out) PM_CHECK(hipFree(q.d_st_out));
-        q.d_st_in = q.d_st_out = nullptr;
-        q.cap_st = 0;
-        const size_t c = std::max(nseg, (size_t)1 << 10);
-        PM_CHECK(hipMalloc(&q.d_st_in, c * sizeof(uint32_t)));
-        PM_CHECK(hipMalloc(&q.d_st_out, c * sizeof(uint32_t)));
-        q.cap_st = c;
-    }
-    const bool grp = ga && ga->stream_groups;
-    if (grp && nseg > q.cap_grp) {
-        if (q.d_grp) PM_CHECK(hipFree(q.d_grp));
-        q.d_grp = nullptr;
-        q.cap_grp = 0;
-        const size_t c = std::max(nseg, (size_t)1 << 10);
-        PM_CHECK(hipMalloc(&q.d_grp, c * sizeof(uint32_t)));
-        q.cap_grp = c;
-    }
-    const bool ps = ga && (ga->windows || (ga->nocase && o->d_win)) && flows && ga->pos;
-    const size_t cwords = ga && ga->nocase && flows && ga->case_hist ? nseg * (size_t)o->nc.dev.W : 0;
-    if (cwords > q.cap_case) {
-        if (q.d_case_in) PM_CHECK(hipFree(q.d_case_in));
-        if (q.d_case_out) PM_CHECK(hipFree(q.d_case_out));
-        q.d_case_in = q.d_case_out = nullptr;
-        q.cap_case = 0;
-        const size_t c = std::max(cwords, (size_t)1 << 10);
-        PM_CHECK(hipMalloc(&q.d_case_in, c * sizeof(uint64_t)));
-        PM_CHECK(hipMalloc(&q.d_case_out, c * sizeof(uint64_t)));
-        q.cap_case = c;
-    }
-    if (ps && nseg > q.cap_pos) {
-        if (q.d_pos_in) PM_CHECK(hipFree(q.d_pos_in));
-        if (q.d_pos_out) PM_CHECK(hipFree(q.d_pos_out));
-        q.d_pos_in = q.d_pos_out = nullptr;
-        q.cap_pos = 0;
-        const size_t c = std::max(nseg, (size_t)1 << 10);
-        PM_CHECK(hipMalloc(&q.d_pos_in, c * sizeof(uint64_t)));
-        PM_CHECK(hipMalloc(&q.d_pos_out, c * sizeof(uint64_t)));
-        q.cap_pos = c;
-    }
+    const bool grp = c.stream_groups != nullptr;
+    const bool ps = o->d_win && c.pos_in;  // without a window table nothing reads the positions
+    const size_t cwords = c.case_in ? nseg * (size_t)o->nc.dev.W : 0;
+    if (st) stage_grow((void**)&q.d_st_in, (void**)&q.d_st_out, sizeof(uint32_t), q.cap_st, nseg);
+    if (grp) stage_grow((void**)&q.d_grp, nullptr, sizeof(uint32_t), q.cap_grp, nseg);
+    if (ps) stage_grow((void**)&q.d_pos_in, (void**)&q.d_pos_out, sizeof(uint64_t), q.cap_pos, nseg);
+    stage_grow((void**)&q.d_case_in, (void**)&q.d_case_out, sizeof(uint64_t), q.cap_case, cwords);
     if (!q.d_nev) PM_CHECK(hipMalloc(&q.d_nev, sizeof(unsigned long long)));
     serve_stop(o);  // a device launch wants the whole device
     PM_CHECK(hipMemcpyAsync(q.d_text, buf, n, hipMemcpyHostToDevice, q.s));
     PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
     if (st) PM_CHECK(hipMemcpyAsync(q.d_st_in, state, nseg * sizeof(uint32_t), hipMemcpyHostToDevice, q.s));
-    if (grp)
-        PM_CHECK(hipMemcpyAsync(q.d_grp, ga->stream_groups, nseg * sizeof(uint32_t), hipMemcpyHostToDevice, q.s));
-    if (ps) PM_CHECK(hipMemcpyAsync(q.d_pos_in, ga->pos, nseg * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
-    if (cwords)
-        PM_CHECK(hipMemcpyAsync(q.d_case_in, ga->case_hist, cwords * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    if (grp) PM_CHECK(hipMemcpyAsync(q.d_grp, c.stream_groups, nseg * sizeof(uint32_t), hipMemcpyHostToDevice, q.s));
+    if (ps) PM_CHECK(hipMemcpyAsync(q.d_pos_in, c.pos_in, nseg * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    if (cwords) PM_CHECK(hipMemcpyAsync(q.d_case_in, c.case_in, cwords * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    // the same call over the staged arrays
+    ListCall dc = c;
+    dc.stream_groups = grp ? q.d_grp : nullptr;
+    dc.pos_in = ps ? q.d_pos_in : nullptr;
+    dc.pos_out = ps ? q.d_pos_out : nullptr;
+    dc.case_in = cwords ? q.d_case_in : nullptr;
+    dc.case_out = cwords ? q.d_case_out : nullptr;
     size_t dcap = o->events_cap > 0 ? (size_t)o->events_cap : std::max<size_t>(1024, n / 16);
     unsigned long long total = 0;
     for (int launch = 0; launch < 2; ++launch) {
@@ -2120,49 +2122,12 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
             q.cap_ev = dcap;
         }
         PM_CHECK(hipMemsetAsync(q.d_nev, 0, sizeof(unsigned long long), q.s));
-        const EvDev ev = events_dev(o, min_len, q.d_ev, dcap, q.d_nev);
-        const uint32_t* const si = st ? q.d_st_in : nullptr;
-        uint32_t* const so = st ? q.d_st_out : nullptr;
-        hipError_t e;
-        if (ga && ga->nocase) {
-            const GroupDev gr = o->d_gmask ? groups_dev(o, grp ? q.d_grp : nullptr) : GroupDev{nullptr, nullptr, nullptr};
-            const WinDev wn = o->d_win ? windows_dev(o, ps ? q.d_pos_in : nullptr, ps ? q.d_pos_out : nullptr)
-                                       : WinDev{nullptr, nullptr, nullptr};
-            const NcDev nc = nocase_dev(o, cwords ? q.d_case_in : nullptr, cwords ? q.d_case_out : nullptr);
-            e = flows ? pm_launch_dfa_flows_nocase(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev, nc, gr, wn,
-                                                   ga->all, nocase_dfa(o), o->nc.dfa_states, o->flow_seg, o->num_cu,
-                                                   q.s)
-                      : pm_launch_rt_batch_nocase(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, nc, gr, wn, ga->all,
-                                                  nocase_rt(o), o->num_cu, q.s);
-        } else if (ga && ga->windows) {
-            const GroupDev gr = groups_dev(o, grp ? q.d_grp : nullptr);
-            const WinDev wn = windows_dev(o, ps ? q.d_pos_in : nullptr, ps ? q.d_pos_out : nullptr);
-            e = flows ? pm_launch_dfa_flows_windows(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev,
-                                                    matches_dev(o), gr, wn, ga->all, o->dfa, o->dfa_states,
-                                                    o->flow_seg, o->num_cu, q.s)
-                      : pm_launch_rt_batch_windows(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, matches_dev(o),
-                                                   gr, wn, ga->all, o->rt, o->num_cu, q.s);
-        } else if (ga) {
-            const GroupDev gr = groups_dev(o, grp ? q.d_grp : nullptr);
-            e = flows ? pm_launch_dfa_flows_groups(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev,
-                                                   matches_dev(o), gr, ga->all, o->dfa, o->dfa_states, o->flow_seg,
-                                                   o->num_cu, q.s)
-                      : pm_launch_rt_batch_groups(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, matches_dev(o), gr,
-                                                  ga->all, o->rt, o->num_cu, q.s);
-        } else if (all)
-            e = flows ? pm_launch_dfa_flows_matches(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev,
-                                                    matches_dev(o), o->dfa, o->dfa_states, o->flow_seg, o->num_cu, q.s)
-                      : pm_launch_rt_batch_matches(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, matches_dev(o),
-                                                   o->rt, o->num_cu, q.s);
-        else
-            e = flows ? pm_launch_dfa_flows_events(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, si, so, ev, o->dfa,
-                                                   o->dfa_states, o->flow_seg, o->num_cu, q.s)
-                      : pm_launch_rt_batch_events(q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n, ev, o->rt, o->num_cu,
-                                                  q.s);
+        const hipError_t e = list_launch(o, flows, dc, q.d_text, q.d_offs, (int64_t)nseg, (int64_t)n,
+                                         st ? q.d_st_in : nullptr, st ? q.d_st_out : nullptr,
+                                         events_dev(o, min_len, q.d_ev, dcap, q.d_nev), q.s);
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(q.s);
-            std::snprintf(g_err, sizeof(g_err), "%s %s launch: %s", flows ? "flow" : "batch",
-                          ga ? (ga->nocase ? "nocase" : ga->windows ? "windows" : "groups") : all ? "matches" : "events",
+            std::snprintf(g_err, sizeof(g_err), "%s %s launch: %s", flows ? "flow" : "batch", LIST_FORM_NAME[c.form],
                           hipGetErrorString(e));
             return -3;
         }
@@ -2176,9 +2141,8 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
     std::vector<uint64_t> ev((size_t)total);
     if (total) PM_CHECK(hipMemcpyAsync(ev.data(), q.d_ev, ev.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
     if (st) PM_CHECK(hipMemcpyAsync(state, q.d_st_out, nseg * sizeof(uint32_t), hipMemcpyDeviceToHost, q.s));
-    if (ps) PM_CHECK(hipMemcpyAsync(ga->pos, q.d_pos_out, nseg * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
-    if (cwords)
-        PM_CHECK(hipMemcpyAsync(ga->case_hist, q.d_case_out, cwords * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    if (ps) PM_CHECK(hipMemcpyAsync(c.pos_out, q.d_pos_out, nseg * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    if (cwords) PM_CHECK(hipMemcpyAsync(c.case_out, q.d_case_out, cwords * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
     PM_CHECK(hipStreamSynchronize(q.s));
     // position order: the position is the high bits; all: then the gid within a position
     std::sort(ev.begin(), ev.end());
@@ -2189,22 +2153,26 @@ static int read_events(PmHip* o, bool flows, bool all, const uint8_t* buf, const
 
 int pm_hip_read_batch_events(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t min_len,
                              uint64_t* events, size_t cap, size_t* nevents) {
-    return read_events(as(obj), false, false, buf, offsets, nseg, nullptr, min_len, events, cap, nevents);
+    return read_events(as(obj), false, ListCall{LIST_EVENTS, false}, buf, offsets, nseg, nullptr, min_len, events, cap,
+                       nevents);
 }
 
 int pm_hip_read_batch_matches(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t min_len,
                               uint64_t* events, size_t cap, size_t* nevents) {
-    return read_events(as(obj), false, true, buf, offsets, nseg, nullptr, min_len, events, cap, nevents);
+    return read_events(as(obj), false, ListCall{LIST_MATCHES, true}, buf, offsets, nseg, nullptr, min_len, events, cap,
+                       nevents);
 }
 
 int pm_hip_read_flows_events(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                              uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents) {
-    return read_events(as(obj), true, false, buf, offsets, nseg, state, min_len, events, cap, nevents);
+    return read_events(as(obj), true, ListCall{LIST_EVENTS, false}, buf, offsets, nseg, state, min_len, events, cap,
+                       nevents);
 }
 
 int pm_hip_read_flows_matches(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                               uint32_t min_len, uint64_t* events, size_t cap, size_t* nevents) {
-    return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents);
+    return read_events(as(obj), true, ListCall{LIST_MATCHES, true}, buf, offsets, nseg, state, min_len, events, cap,
+                       nevents);
 }
 
 // ---- pattern groups (pm_hip.h, "pattern groups") -----------------------------
@@ -2246,80 +2214,30 @@ int pm_hip_scan_batch_groups_device(void* obj, const uint8_t* d_text, const int6
                                     int64_t n, const uint32_t* d_stream_groups, uint32_t min_len, int all,
                                     uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
                                     void* hip_stream) {
-    PmHip* o = as(obj);
-    if (const int rc = batch_check(o)) return rc;
-    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) ||
-        ((uintptr_t)d_stream_groups & 3) || (nseg > 0 && n > 0 && (!d_text || !d_offsets))) {
-        std::snprintf(g_err, sizeof(g_err),
-                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned, stream groups 4-B "
-                      "aligned)");
-        return -2;
-    }
-    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
-    if (const int rc = events_gid_check(o)) return rc;
-    if (const int rc = groups_check(o)) return rc;
-    if (nseg == 0 || n == 0) return 0;
-    hipError_t e = hipSetDevice(o->device);
-    serve_stop(o);  // a device launch wants the whole device
-    if (e == hipSuccess)
-        e = pm_launch_rt_batch_groups(d_text, d_offsets, nseg, n, events_dev(o, min_len, d_events, cap, d_nevents),
-                                      matches_dev(o), groups_dev(o, d_stream_groups), all != 0, o->rt, o->num_cu,
-                                      (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        std::snprintf(g_err, sizeof(g_err), "batch groups launch: %s", hipGetErrorString(e));
-        return -3;
-    }
-    o->last_kernel = KIND_RT;
-    o->last_form = 0;
-    return 0;
+    return scan_list_device(as(obj), false, ListCall{LIST_GROUPS, all != 0, d_stream_groups}, d_text, d_offsets, nseg, n, nullptr,
+                            nullptr, min_len, d_events, cap, d_nevents, hip_stream);
 }
 
 int pm_hip_scan_flows_groups_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
                                     int64_t n, const uint32_t* d_state_in, uint32_t* d_state_out,
                                     const uint32_t* d_stream_groups, uint32_t min_len, int all, uint64_t* d_events,
                                     uint64_t cap, unsigned long long* d_nevents, void* hip_stream) {
-    PmHip* o = as(obj);
-    if (const int rc = flows_check(o)) return rc;
-    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_state_in & 3) ||
-        ((uintptr_t)d_state_out & 3) || ((uintptr_t)d_stream_groups & 3) ||
-        (d_state_in && d_state_in == d_state_out) || (nseg > 0 && (!d_offsets || (n > 0 && !d_text)))) {
-        std::snprintf(g_err, sizeof(g_err),
-                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned, states and stream "
-                      "groups 4-B aligned, state_in != state_out)");
-        return -2;
-    }
-    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
-    if (const int rc = events_gid_check(o)) return rc;
-    if (const int rc = groups_check(o)) return rc;
-    if (nseg == 0 || (n == 0 && !d_state_out)) return 0;
-    hipError_t e = hipSetDevice(o->device);
-    serve_stop(o);  // a device launch wants the whole device
-    if (e == hipSuccess)
-        e = pm_launch_dfa_flows_groups(d_text, d_offsets, nseg, n, d_state_in, d_state_out,
-                                       events_dev(o, min_len, d_events, cap, d_nevents), matches_dev(o),
-                                       groups_dev(o, d_stream_groups), all != 0, o->dfa, o->dfa_states, o->flow_seg,
-                                       o->num_cu, (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        std::snprintf(g_err, sizeof(g_err), "flow groups launch: %s", hipGetErrorString(e));
-        return -3;
-    }
-    o->last_kernel = KIND_AC;
-    o->last_form = 1;
-    return 0;
+    return scan_list_device(as(obj), true, ListCall{LIST_GROUPS, all != 0, d_stream_groups}, d_text,
+                            d_offsets, nseg, n, d_state_in, d_state_out, min_len, d_events, cap, d_nevents, hip_stream);
 }
 
 int pm_hip_read_batch_groups(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg,
                              const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
                              size_t* nevents) {
-    const GroupArgs ga{stream_groups, all != 0};
-    return read_events(as(obj), false, true, buf, offsets, nseg, nullptr, min_len, events, cap, nevents, &ga);
+    return read_events(as(obj), false, ListCall{LIST_GROUPS, all != 0, stream_groups}, buf, offsets, nseg, nullptr, min_len,
+                       events, cap, nevents);
 }
 
 int pm_hip_read_flows_groups(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                              const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
                              size_t* nevents) {
-    const GroupArgs ga{stream_groups, all != 0};
-    return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents, &ga);
+    return read_events(as(obj), true, ListCall{LIST_GROUPS, all != 0, stream_groups}, buf, offsets, nseg, state,
+                       min_len, events, cap, nevents);
 }
 
 // ---- pattern windows (pm_hip.h, "pattern windows") ---------------------------
@@ -2365,33 +2283,8 @@ int pm_hip_scan_batch_windows_device(void* obj, const uint8_t* d_text, const int
                                      int64_t n, const uint32_t* d_stream_groups, uint32_t min_len, int all,
                                      uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
                                      void* hip_stream) {
-    PmHip* o = as(obj);
-    if (const int rc = batch_check(o)) return rc;
-    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) ||
-        ((uintptr_t)d_stream_groups & 3) || (nseg > 0 && n > 0 && (!d_text || !d_offsets))) {
-        std::snprintf(g_err, sizeof(g_err),
-                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned, stream groups 4-B "
-                      "aligned)");
-        return -2;
-    }
-    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
-    if (const int rc = events_gid_check(o)) return rc;
-    if (const int rc = windows_check(o, d_stream_groups)) return rc;
-    if (nseg == 0 || n == 0) return 0;
-    hipError_t e = hipSetDevice(o->device);
-    serve_stop(o);  // a device launch wants the whole device
-    if (e == hipSuccess)
-        e = pm_launch_rt_batch_windows(d_text, d_offsets, nseg, n, events_dev(o, min_len, d_events, cap, d_nevents),
-                                       matches_dev(o), groups_dev(o, d_stream_groups),
-                                       windows_dev(o, nullptr, nullptr), all != 0, o->rt, o->num_cu,
-                                       (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        std::snprintf(g_err, sizeof(g_err), "batch windows launch: %s", hipGetErrorString(e));
-        return -3;
-    }
-    o->last_kernel = KIND_RT;
-    o->last_form = 0;
-    return 0;
+    return scan_list_device(as(obj), false, ListCall{LIST_WINDOWS, all != 0, d_stream_groups}, d_text, d_offsets, nseg, n, nullptr,
+                            nullptr, min_len, d_events, cap, d_nevents, hip_stream);
 }
 
 int pm_hip_scan_flows_windows_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
@@ -2399,49 +2292,22 @@ int pm_hip_scan_flows_windows_device(void* obj, const uint8_t* d_text, const int
                                      const uint32_t* d_stream_groups, uint32_t min_len, int all, uint64_t* d_events,
                                      uint64_t cap, unsigned long long* d_nevents, void* hip_stream,
                                      const uint64_t* d_pos_in, uint64_t* d_pos_out) {
-    PmHip* o = as(obj);
-    if (const int rc = flows_check(o)) return rc;
-    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_state_in & 3) ||
-        ((uintptr_t)d_state_out & 3) || ((uintptr_t)d_stream_groups & 3) || ((uintptr_t)d_pos_in & 7) ||
-        ((uintptr_t)d_pos_out & 7) || (d_state_in && d_state_in == d_state_out) ||
-        (d_pos_in && d_pos_in == d_pos_out) || (nseg > 0 && (!d_offsets || (n > 0 && !d_text)))) {
-        std::snprintf(g_err, sizeof(g_err),
-                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets and positions 8-B aligned, states "
-                      "and stream groups 4-B aligned, state_in != state_out, pos_in != pos_out)");
-        return -2;
-    }
-    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
-    if (const int rc = events_gid_check(o)) return rc;
-    if (const int rc = windows_check(o, d_stream_groups)) return rc;
-    if (nseg == 0 || (n == 0 && !d_state_out && !d_pos_out)) return 0;
-    hipError_t e = hipSetDevice(o->device);
-    serve_stop(o);  // a device launch wants the whole device
-    if (e == hipSuccess)
-        e = pm_launch_dfa_flows_windows(d_text, d_offsets, nseg, n, d_state_in, d_state_out,
-                                        events_dev(o, min_len, d_events, cap, d_nevents), matches_dev(o),
-                                        groups_dev(o, d_stream_groups), windows_dev(o, d_pos_in, d_pos_out), all != 0,
-                                        o->dfa, o->dfa_states, o->flow_seg, o->num_cu, (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        std::snprintf(g_err, sizeof(g_err), "flow windows launch: %s", hipGetErrorString(e));
-        return -3;
-    }
-    o->last_kernel = KIND_AC;
-    o->last_form = 1;
-    return 0;
+    return scan_list_device(as(obj), true, ListCall{LIST_WINDOWS, all != 0, d_stream_groups, d_pos_in, d_pos_out}, d_text,
+                            d_offsets, nseg, n, d_state_in, d_state_out, min_len, d_events, cap, d_nevents, hip_stream);
 }
 
 int pm_hip_read_batch_windows(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg,
                               const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
                               size_t* nevents) {
-    const GroupArgs ga{stream_groups, all != 0, true, nullptr};
-    return read_events(as(obj), false, true, buf, offsets, nseg, nullptr, min_len, events, cap, nevents, &ga);
+    return read_events(as(obj), false, ListCall{LIST_WINDOWS, all != 0, stream_groups}, buf, offsets, nseg, nullptr, min_len,
+                       events, cap, nevents);
 }
 
 int pm_hip_read_flows_windows(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                               uint64_t* pos, const uint32_t* stream_groups, uint32_t min_len, int all,
                               uint64_t* events, size_t cap, size_t* nevents) {
-    const GroupArgs ga{stream_groups, all != 0, true, pos};
-    return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents, &ga);
+    return read_events(as(obj), true, ListCall{LIST_WINDOWS, all != 0, stream_groups, pos, pos}, buf, offsets, nseg, state,
+                       min_len, events, cap, nevents);
 }
 
 // ---- per-pattern nocase (pm_hip.h, "nocase") ---------------------------------
@@ -2551,34 +2417,8 @@ int pm_hip_scan_batch_nocase_device(void* obj, const uint8_t* d_text, const int6
                                     int64_t n, const uint32_t* d_stream_groups, uint32_t min_len, int all,
                                     uint64_t* d_events, uint64_t cap, unsigned long long* d_nevents,
                                     void* hip_stream) {
-    PmHip* o = as(obj);
-    if (const int rc = batch_check(o)) return rc;
-    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) ||
-        ((uintptr_t)d_stream_groups & 3) || (nseg > 0 && n > 0 && (!d_text || !d_offsets))) {
-        std::snprintf(g_err, sizeof(g_err),
-                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets 8-B aligned, stream groups 4-B "
-                      "aligned)");
-        return -2;
-    }
-    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
-    if (const int rc = events_gid_check(o)) return rc;
-    if (const int rc = nocase_check(o, false, d_stream_groups)) return rc;
-    if (nseg == 0 || n == 0) return 0;
-    hipError_t e = hipSetDevice(o->device);
-    serve_stop(o);  // a device launch wants the whole device
-    if (e == hipSuccess)
-        e = pm_launch_rt_batch_nocase(d_text, d_offsets, nseg, n, events_dev(o, min_len, d_events, cap, d_nevents),
-                                      nocase_dev(o, nullptr, nullptr),
-                                      o->d_gmask ? groups_dev(o, d_stream_groups) : GroupDev{nullptr, nullptr, nullptr},
-                                      o->d_win ? windows_dev(o, nullptr, nullptr) : WinDev{nullptr, nullptr, nullptr},
-                                      all != 0, nocase_rt(o), o->num_cu, (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        std::snprintf(g_err, sizeof(g_err), "batch nocase launch: %s", hipGetErrorString(e));
-        return -3;
-    }
-    o->last_kernel = KIND_RT;
-    o->last_form = 0;
-    return 0;
+    return scan_list_device(as(obj), false, ListCall{LIST_NOCASE, all != 0, d_stream_groups}, d_text, d_offsets, nseg, n, nullptr,
+                            nullptr, min_len, d_events, cap, d_nevents, hip_stream);
 }
 
 int pm_hip_scan_flows_nocase_device(void* obj, const uint8_t* d_text, const int64_t* d_offsets, int64_t nseg,
@@ -2587,62 +2427,23 @@ int pm_hip_scan_flows_nocase_device(void* obj, const uint8_t* d_text, const int6
                                     uint64_t cap, unsigned long long* d_nevents, void* hip_stream,
                                     const uint64_t* d_pos_in, uint64_t* d_pos_out, const uint64_t* d_case_in,
                                     uint64_t* d_case_out) {
-    PmHip* o = as(obj);
-    if (const int rc = flows_check(o)) return rc;
-    if (nseg < 0 || n < 0 || ((uintptr_t)d_text & 15) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_state_in & 3) ||
-        ((uintptr_t)d_state_out & 3) || ((uintptr_t)d_stream_groups & 3) || ((uintptr_t)d_pos_in & 7) ||
-        ((uintptr_t)d_pos_out & 7) || (d_state_in && d_state_in == d_state_out) ||
-        (d_pos_in && d_pos_in == d_pos_out) || (nseg > 0 && (!d_offsets || (n > 0 && !d_text)))) {
-        std::snprintf(g_err, sizeof(g_err),
-                      "bad arguments (nseg >= 0, n >= 0, text 16-B aligned, offsets and positions 8-B aligned, states "
-                      "and stream groups 4-B aligned, state_in != state_out, pos_in != pos_out)");
-        return -2;
-    }
-    if (const int rc = events_args_check(n, min_len, d_events, cap, d_nevents, true)) return rc;
-    if (const int rc = events_gid_check(o)) return rc;
-    if (const int rc = nocase_check(o, true, d_stream_groups)) return rc;
-    if (o->nc.dev.W && (((uintptr_t)d_case_in & 7) || ((uintptr_t)d_case_out & 7) ||
-                        (d_case_in && d_case_in == d_case_out))) {
-        std::snprintf(g_err, sizeof(g_err), "bad arguments (case histories 8-B aligned, case_in != case_out)");
-        return -2;
-    }
-    const bool hist = o->nc.dev.W && d_case_out;
-    const bool pos = o->d_win && d_pos_out;
-    if (nseg == 0 || (n == 0 && !d_state_out && !pos && !hist)) return 0;
-    hipError_t e = hipSetDevice(o->device);
-    serve_stop(o);  // a device launch wants the whole device
-    if (e == hipSuccess)
-        e = pm_launch_dfa_flows_nocase(
-            d_text, d_offsets, nseg, n, d_state_in, d_state_out, events_dev(o, min_len, d_events, cap, d_nevents),
-            nocase_dev(o, d_case_in, d_case_out),
-            o->d_gmask ? groups_dev(o, d_stream_groups) : GroupDev{nullptr, nullptr, nullptr},
-            o->d_win ? windows_dev(o, d_pos_in, d_pos_out) : WinDev{nullptr, nullptr, nullptr}, all != 0, nocase_dfa(o),
-            o->nc.dfa_states, o->flow_seg, o->num_cu, (hipStream_t)hip_stream);
-    if (e != hipSuccess) {
-        std::snprintf(g_err, sizeof(g_err), "flow nocase launch: %s", hipGetErrorString(e));
-        return -3;
-    }
-    o->last_kernel = KIND_AC;
-    o->last_form = 1;
-    return 0;
+    return scan_list_device(
+        as(obj), true, ListCall{LIST_NOCASE, all != 0, d_stream_groups, d_pos_in, d_pos_out, d_case_in, d_case_out},
+        d_text, d_offsets, nseg, n, d_state_in, d_state_out, min_len, d_events, cap, d_nevents, hip_stream);
 }
 
 int pm_hip_read_batch_nocase(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg,
                              const uint32_t* stream_groups, uint32_t min_len, int all, uint64_t* events, size_t cap,
                              size_t* nevents) {
-    GroupArgs ga{stream_groups, all != 0};
-    ga.nocase = true;
-    return read_events(as(obj), false, true, buf, offsets, nseg, nullptr, min_len, events, cap, nevents, &ga);
+    return read_events(as(obj), false, ListCall{LIST_NOCASE, all != 0, stream_groups}, buf, offsets, nseg, nullptr, min_len,
+                       events, cap, nevents);
 }
 
 int pm_hip_read_flows_nocase(void* obj, const uint8_t* buf, const int64_t* offsets, size_t nseg, uint32_t* state,
                              uint64_t* pos, uint64_t* case_hist, const uint32_t* stream_groups, uint32_t min_len,
                              int all, uint64_t* events, size_t cap, size_t* nevents) {
-    GroupArgs ga{stream_groups, all != 0};
-    ga.pos = pos;
-    ga.nocase = true;
-    ga.case_hist = case_hist;
-    return read_events(as(obj), true, true, buf, offsets, nseg, state, min_len, events, cap, nevents, &ga);
+    return read_events(as(obj), true, ListCall{LIST_NOCASE, all != 0, stream_groups, pos, pos, case_hist, case_hist},
+                       buf, offsets, nseg, state, min_len, events, cap, nevents);
 }
 
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,

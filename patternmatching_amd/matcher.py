@@ -121,6 +121,23 @@ def batch_offsets(buffers) -> np.ndarray:
     return offs
 
 
+def _concat(buffers):
+    """(data, offsets) of a list of bytes-like streams: their bytes back to
+    back as one u8 array, and batch_offsets of them."""
+    parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
+             else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
+    return (np.concatenate(parts) if parts else np.empty(0, np.uint8)), batch_offsets(buffers)
+
+
+def _unique_keys(keys, name):
+    """ValueError where a flow key comes twice in the packets of one
+    FlowTable call (name: the method called)."""
+    if len(set(keys)) != len(keys):
+        seen = set()
+        dup = next(k for k in keys if k in seen or seen.add(k))
+        raise ValueError(f"flow {dup!r} appears twice in one {name}(): concatenate its packets")
+
+
 EVENT_GID_BITS = 24
 
 
@@ -166,17 +183,10 @@ class FlowTable:
         """packets: a list of (key, bytes-like).  Returns the codes of each
         packet, in order, every flow continued from its earlier packets."""
         keys = [k for k, _ in packets]
-        if len(set(keys)) != len(keys):
-            seen = set()
-            dup = next(k for k in keys if k in seen or seen.add(k))
-            raise ValueError(f"flow {dup!r} appears twice in one scan(): concatenate its packets")
+        _unique_keys(keys, "scan")
         if not packets:
             return []
-        bufs = [b for _, b in packets]
-        offs = batch_offsets(bufs)
-        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
-                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in bufs]
-        data = np.concatenate(parts)
+        data, offs = _concat([b for _, b in packets])
         state = np.array([self.states.get(k, 0) for k in keys], dtype=np.uint32)
         codes, state = self.matcher.read_flows_codes(data, offs, state)
         for k, s in zip(keys, state.tolist()):
@@ -238,21 +248,14 @@ class FlowTable:
         if packets and len(packets[0]) == 3:
             grp = np.array([g for _, _, g in packets], dtype=np.uint32)
         keys = [p[0] for p in packets]
-        if len(set(keys)) != len(keys):
-            seen = set()
-            dup = next(k for k in keys if k in seen or seen.add(k))
-            raise ValueError(f"flow {dup!r} appears twice in one scan_nocase(): concatenate its packets")
+        _unique_keys(keys, "scan_nocase")
         for k in keys:
             if self.bytes.get(k, 0) != self.nocase_bytes.get(k, 0):
                 raise ValueError(f"flow {k!r} has had {self.bytes.get(k, 0)} bytes but scan_nocase() saw "
                                  f"{self.nocase_bytes.get(k, 0)} of them")
         if not packets:
             return []
-        bufs = [p[1] for p in packets]
-        offs = batch_offsets(bufs)
-        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
-                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in bufs]
-        data = np.concatenate(parts)
+        data, offs = _concat([p[1] for p in packets])
         W = self.matcher.case_words
         state = np.array([self.nocase_states.get(k, 0) for k in keys], dtype=np.uint32)
         pos_in = np.array([self.bytes.get(k, 0) for k in keys], dtype=np.uint64)
@@ -276,17 +279,10 @@ class FlowTable:
 
     def _scan_list(self, packets, min_len, read, name):
         keys = [k for k, _ in packets]
-        if len(set(keys)) != len(keys):
-            seen = set()
-            dup = next(k for k in keys if k in seen or seen.add(k))
-            raise ValueError(f"flow {dup!r} appears twice in one {name}(): concatenate its packets")
+        _unique_keys(keys, name)
         if not packets:
             return []
-        bufs = [b for _, b in packets]
-        offs = batch_offsets(bufs)
-        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
-                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in bufs]
-        data = np.concatenate(parts)
+        data, offs = _concat([b for _, b in packets])
         state = np.array([self.states.get(k, 0) for k in keys], dtype=np.uint32)
         pos, codes, state = read(data, offs, state, min_len)
         for k, s in zip(keys, state.tolist()):
@@ -391,6 +387,11 @@ class HipMatcher:
         them); 0 on success, -1 for an unknown name or value."""
         return self.lib.pm_hip_set_option(self.obj, name.encode(), int(value))
 
+    def _check(self, rc):
+        """RuntimeError with the library's message for a call that returned rc != 0."""
+        if rc != 0:
+            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+
     # --- batch ---------------------------------------------------------
     def read_block_gids(self, data) -> np.ndarray:
         arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
@@ -417,8 +418,7 @@ class HipMatcher:
         out_width bytes (4 = u32, 2 = u16) to d_out_ptr, or count only."""
         fn = {4: self.lib.pm_hip_scan_device, 2: self.lib.pm_hip_scan_device16}[out_width]
         rc = fn(self.obj, d_text_ptr, stream_start, pos0, n, d_out_ptr, d_count_ptr, stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     # --- batched scan: many independent streams in one launch ------------
     def scan_batch_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_out_ptr, d_count_ptr, stream_ptr, out_width=4):
@@ -428,8 +428,7 @@ class HipMatcher:
         only.  Every stream is scanned from its own first byte."""
         fn = {4: self.lib.pm_hip_scan_batch_device, 2: self.lib.pm_hip_scan_batch_device16}[out_width]
         rc = fn(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_out_ptr, d_count_ptr, stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def read_batch_gids(self, data, offsets, out=None) -> np.ndarray:
         """pm_hip_read_batch_gid: gids (u32) of the streams data[offsets[j]:
@@ -449,8 +448,7 @@ class HipMatcher:
         rc = self.lib.pm_hip_read_batch_gid(self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                                             offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), offs.size - 1,
                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
         return out
 
     def read_batch_codes(self, data, offsets) -> np.ndarray:
@@ -468,17 +466,13 @@ class HipMatcher:
         rc = self.lib.pm_hip_read_batch(self.obj, arr.ctypes.data_as(ctypes.c_char_p),
                                         offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), offs.size - 1,
                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)))
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
         return out[:len(arr)]
 
     def read_many_codes(self, buffers):
         """One batch call over a list of bytes-like streams; the codes of
         each, in order."""
-        offs = batch_offsets(buffers)
-        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
-                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
-        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        data, offs = _concat(buffers)
         codes = self.read_batch_codes(data, offs)
         return [codes[offs[j]:offs[j + 1]] for j in range(len(buffers))]
 
@@ -495,8 +489,7 @@ class HipMatcher:
         device u64 cursor d_nevents_ptr into d_events_ptr[0, cap)."""
         rc = self.lib.pm_hip_scan_batch_events_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, min_len,
                                                       d_events_ptr, cap, d_nevents_ptr, stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def scan_flows_events_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr, min_len,
                                  d_events_ptr, cap, d_nevents_ptr, stream_ptr):
@@ -505,53 +498,66 @@ class HipMatcher:
         rc = self.lib.pm_hip_scan_flows_events_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr,
                                                       d_state_out_ptr, min_len, d_events_ptr, cap, d_nevents_ptr,
                                                       stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
-    def _read_events(self, data, offsets, state, min_len, all_matches=False, stream_groups=None):
-        """The host events forms (all_matches: the *_matches ones;
-        stream_groups: the *_groups ones, in the form all_matches names):
-        (events u64 ascending, state_out or None).  A host buffer too short
-        for the call's events means one more call with room for all of them,
-        from the same states."""
+    def _read_list(self, form, data, offsets, min_len, all_matches, stream_groups=None, state=None, pos=None,
+                   case=None):
+        """The host list forms, pm_hip_read_{batch,flows}_<form>: form is
+        "events", "matches", "groups", "windows" or "nocase"; state None is
+        the batched call, an array the flow one.  Returns (events u64
+        ascending, state_out, pos_out, case_out), each of the last three None
+        where it was not passed.  A host buffer too short for the call's
+        events means one more call with room for all of them, from the same
+        states, positions and histories."""
         arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
                                    else data, dtype=np.uint8)
         offs = np.ascontiguousarray(offsets, dtype=np.int64)
         if offs.ndim != 1 or offs.size < 1 or int(offs[-1]) != len(arr):
             raise ValueError("offsets: nseg + 1 values, the last one len(data)")
         nseg = offs.size - 1
-        if state is not None and state.shape != (nseg,):
-            raise ValueError("state: nseg values")
+        for name, a in (("state", state), ("pos", pos)):
+            if a is not None and a.shape != (nseg,):
+                raise ValueError(f"{name}: nseg values")
+        if case is not None and case.shape != (nseg, self.case_words):
+            raise ValueError("case: nseg rows of case_words values")
+        grp = None
         if stream_groups is not None:
             grp = np.ascontiguousarray(stream_groups, dtype=np.uint32)
             if grp.shape != (nseg,):
                 raise ValueError("stream_groups: nseg values")
+        u32p, u64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+
+        def ptr(a, t):
+            return None if a is None else a.ctypes.data_as(t)
+        fn = getattr(self.lib, f"pm_hip_read_{'batch' if state is None else 'flows'}_{form}")
         cap = max(1024, len(arr) // 16)
         while True:
             ev = np.empty(cap, dtype=np.uint64)
             total = ctypes.c_size_t(0)
-            st = None if state is None else state.copy()
-            head = (self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                    offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg)
-            tail = (min_len, ev.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), cap, ctypes.byref(total))
-            if stream_groups is not None:
-                tail = (grp.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), min_len, int(bool(all_matches))) + tail[1:]
-                if state is None:
-                    rc = self.lib.pm_hip_read_batch_groups(*head, *tail)
-                else:
-                    rc = self.lib.pm_hip_read_flows_groups(*head, st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                                           *tail)
-            elif state is None:
-                fn = self.lib.pm_hip_read_batch_matches if all_matches else self.lib.pm_hip_read_batch_events
-                rc = fn(*head, *tail)
+            st, ps, cs = (None if a is None else a.copy() for a in (state, pos, case))
+            args = [self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                    offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg]
+            if state is not None:  # what a flow carries, as far as the form has it
+                args.append(st.ctypes.data_as(u32p))
+                if form in ("windows", "nocase"):
+                    args.append(ptr(ps, u64p))
+                if form == "nocase":
+                    args.append(ptr(cs if cs is not None and cs.size else None, u64p))  # no words: NULL
+            if form in ("events", "matches"):
+                args.append(min_len)
             else:
-                fn = self.lib.pm_hip_read_flows_matches if all_matches else self.lib.pm_hip_read_flows_events
-                rc = fn(*head, st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), *tail)
-            if rc != 0:
-                raise RuntimeError(self.lib.pm_hip_last_error().decode())
+                args += [ptr(grp, u32p), min_len, int(bool(all_matches))]
+            self._check(fn(*args, ev.ctypes.data_as(u64p), cap, ctypes.byref(total)))
             if total.value <= cap:
-                return ev[:total.value], st
+                return ev[:total.value], st, ps, cs
             cap = total.value
+
+    def _read_events(self, data, offsets, state, min_len, all_matches=False, stream_groups=None):
+        """_read_list for the events forms (all_matches: the *_matches ones;
+        stream_groups: the *_groups ones, in the form all_matches names):
+        (events u64 ascending, state_out or None)."""
+        form = "groups" if stream_groups is not None else "matches" if all_matches else "events"
+        return self._read_list(form, data, offsets, min_len, all_matches, stream_groups, state)[:2]
 
     def read_batch_events(self, data, offsets, min_len=3):
         """pm_hip_read_batch_events: (positions int64, codes) of the positions
@@ -564,10 +570,7 @@ class HipMatcher:
     def read_many_events(self, buffers, min_len=3):
         """One batch events call over a list of bytes-like streams: per
         stream, in order, (positions inside the stream, codes)."""
-        offs = batch_offsets(buffers)
-        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
-                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
-        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        data, offs = _concat(buffers)
         pos, codes = self.read_batch_events(data, offs, min_len)
         return _split_events(pos, codes, offs)
 
@@ -590,8 +593,7 @@ class HipMatcher:
         cursor may end above n."""
         rc = self.lib.pm_hip_scan_batch_matches_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, min_len,
                                                        d_events_ptr, cap, d_nevents_ptr, stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def scan_flows_matches_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr, min_len,
                                   d_events_ptr, cap, d_nevents_ptr, stream_ptr):
@@ -600,8 +602,7 @@ class HipMatcher:
         rc = self.lib.pm_hip_scan_flows_matches_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr,
                                                        d_state_out_ptr, min_len, d_events_ptr, cap, d_nevents_ptr,
                                                        stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def read_batch_matches(self, data, offsets, min_len=3):
         """pm_hip_read_batch_matches: read_batch_events with every pattern
@@ -613,10 +614,7 @@ class HipMatcher:
 
     def read_many_matches(self, buffers, min_len=3):
         """read_many_events with every pattern that ends at a position."""
-        offs = batch_offsets(buffers)
-        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
-                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
-        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        data, offs = _concat(buffers)
         pos, codes = self.read_batch_matches(data, offs, min_len)
         return _split_events(pos, codes, offs)
 
@@ -639,8 +637,7 @@ class HipMatcher:
         if g.ndim != 1:
             raise ValueError("masks: one u32 per pattern added")
         rc = self.lib.pm_hip_set_groups(self.obj, g.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), g.size)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def pattern_groups(self, gid):
         """The group mask of pattern gid (0 out of range or before set_groups)."""
@@ -656,8 +653,7 @@ class HipMatcher:
         rc = self.lib.pm_hip_scan_batch_groups_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n,
                                                       d_stream_groups_ptr, min_len, int(bool(all_matches)),
                                                       d_events_ptr, cap, d_nevents_ptr, stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def scan_flows_groups_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr,
                                  d_stream_groups_ptr, min_len, all_matches, d_events_ptr, cap, d_nevents_ptr,
@@ -669,8 +665,7 @@ class HipMatcher:
                                                       d_state_out_ptr, d_stream_groups_ptr, min_len,
                                                       int(bool(all_matches)), d_events_ptr, cap, d_nevents_ptr,
                                                       stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def read_batch_groups(self, data, offsets, stream_groups, min_len=3, all_matches=True):
         """pm_hip_read_batch_groups: read_batch_matches with the patterns
@@ -682,10 +677,7 @@ class HipMatcher:
 
     def read_many_groups(self, buffers, stream_groups, min_len=3, all_matches=True):
         """read_many_matches with a group mask per buffer."""
-        offs = batch_offsets(buffers)
-        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
-                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
-        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        data, offs = _concat(buffers)
         pos, codes = self.read_batch_groups(data, offs, stream_groups, min_len, all_matches)
         return _split_events(pos, codes, offs)
 
@@ -710,8 +702,7 @@ class HipMatcher:
             raise ValueError("min_start, max_end: one u32 each per pattern added")
         u32p = ctypes.POINTER(ctypes.c_uint32)
         rc = self.lib.pm_hip_set_windows(self.obj, lo.ctypes.data_as(u32p), hi.ctypes.data_as(u32p), lo.size)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def pattern_window(self, gid):
         """(min_start, max_end) of pattern gid; None out of range or before
@@ -730,8 +721,7 @@ class HipMatcher:
         rc = self.lib.pm_hip_scan_batch_windows_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n,
                                                        d_stream_groups_ptr, min_len, int(bool(all_matches)),
                                                        d_events_ptr, cap, d_nevents_ptr, stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def scan_flows_windows_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr,
                                   d_stream_groups_ptr, min_len, all_matches, d_events_ptr, cap, d_nevents_ptr,
@@ -744,64 +734,20 @@ class HipMatcher:
                                                        d_state_out_ptr, d_stream_groups_ptr, min_len,
                                                        int(bool(all_matches)), d_events_ptr, cap, d_nevents_ptr,
                                                        stream_ptr, d_pos_in_ptr, d_pos_out_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
-
-    def _read_windows(self, data, offsets, stream_groups, state, pos, min_len, all_matches):
-        """The host window forms: (events u64 ascending, state_out or None,
-        pos_out or None); a short host buffer means one more call, as in
-        _read_events."""
-        arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
-                                   else data, dtype=np.uint8)
-        offs = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offs.ndim != 1 or offs.size < 1 or int(offs[-1]) != len(arr):
-            raise ValueError("offsets: nseg + 1 values, the last one len(data)")
-        nseg = offs.size - 1
-        for name, a in (("state", state), ("pos", pos)):
-            if a is not None and a.shape != (nseg,):
-                raise ValueError(f"{name}: nseg values")
-        grp = None
-        if stream_groups is not None:
-            grp = np.ascontiguousarray(stream_groups, dtype=np.uint32)
-            if grp.shape != (nseg,):
-                raise ValueError("stream_groups: nseg values")
-        u32p, u64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
-        cap = max(1024, len(arr) // 16)
-        while True:
-            ev = np.empty(cap, dtype=np.uint64)
-            total = ctypes.c_size_t(0)
-            st = None if state is None else state.copy()
-            ps = None if pos is None else pos.copy()
-            head = (self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                    offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg)
-            tail = (None if grp is None else grp.ctypes.data_as(u32p), min_len, int(bool(all_matches)),
-                    ev.ctypes.data_as(u64p), cap, ctypes.byref(total))
-            if state is None:
-                rc = self.lib.pm_hip_read_batch_windows(*head, *tail)
-            else:
-                rc = self.lib.pm_hip_read_flows_windows(*head, st.ctypes.data_as(u32p),
-                                                        None if ps is None else ps.ctypes.data_as(u64p), *tail)
-            if rc != 0:
-                raise RuntimeError(self.lib.pm_hip_last_error().decode())
-            if total.value <= cap:
-                return ev[:total.value], st, ps
-            cap = total.value
+        self._check(rc)
 
     def read_batch_windows(self, data, offsets, stream_groups=None, min_len=3, all_matches=True):
         """pm_hip_read_batch_windows: read_batch_groups with the patterns'
         windows applied (stream_groups None: every stream on all groups):
         (positions int64, codes), ascending by position, then gid."""
-        ev, _, _ = self._read_windows(data, offsets, stream_groups, None, None, min_len, all_matches)
+        ev = self._read_list("windows", data, offsets, min_len, all_matches, stream_groups)[0]
         pos, gids = unpack_events(ev)
         return pos, self._codes[gids]
 
     def read_many_windows(self, buffers, stream_groups=None, min_len=3, all_matches=True):
         """read_many_groups with the patterns' windows applied, each buffer a
         stream of its own."""
-        offs = batch_offsets(buffers)
-        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
-                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
-        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        data, offs = _concat(buffers)
         pos, codes = self.read_batch_windows(data, offs, stream_groups, min_len, all_matches)
         return _split_events(pos, codes, offs)
 
@@ -814,7 +760,7 @@ class HipMatcher:
         nseg = len(offsets) - 1
         st = np.zeros(nseg, dtype=np.uint32) if state is None else np.array(state, dtype=np.uint32, order="C")
         ps = np.zeros(nseg, dtype=np.uint64) if pos is None else np.array(pos, dtype=np.uint64, order="C")
-        ev, st, ps = self._read_windows(data, offsets, stream_groups, st, ps, min_len, all_matches)
+        ev, st, ps, _ = self._read_list("windows", data, offsets, min_len, all_matches, stream_groups, st, ps)
         p, gids = unpack_events(ev)
         return p, self._codes[gids], st, ps
 
@@ -828,8 +774,7 @@ class HipMatcher:
         if f.ndim != 1:
             raise ValueError("flags: one value per pattern added")
         rc = self.lib.pm_hip_set_nocase(self.obj, f.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), f.size)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def pattern_nocase(self, gid):
         """The nocase flag of pattern gid (bool); None out of range or before
@@ -865,8 +810,7 @@ class HipMatcher:
         rc = self.lib.pm_hip_scan_batch_nocase_device(self.obj, d_text_ptr, d_offsets_ptr, nseg, n,
                                                       d_stream_groups_ptr, min_len, int(bool(all_matches)),
                                                       d_events_ptr, cap, d_nevents_ptr, stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def scan_flows_nocase_device(self, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr,
                                  d_stream_groups_ptr, min_len, all_matches, d_events_ptr, cap, d_nevents_ptr,
@@ -880,53 +824,12 @@ class HipMatcher:
                                                       int(bool(all_matches)), d_events_ptr, cap, d_nevents_ptr,
                                                       stream_ptr, d_pos_in_ptr, d_pos_out_ptr, d_case_in_ptr,
                                                       d_case_out_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def _read_nocase(self, data, offsets, stream_groups, state, pos, case, min_len, all_matches):
-        """The host nocase forms: (events u64 ascending, state_out, pos_out,
-        case_out -- None for the batched form); a short host buffer means one
-        more call, as in _read_events."""
-        arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray)
-                                   else data, dtype=np.uint8)
-        offs = np.ascontiguousarray(offsets, dtype=np.int64)
-        if offs.ndim != 1 or offs.size < 1 or int(offs[-1]) != len(arr):
-            raise ValueError("offsets: nseg + 1 values, the last one len(data)")
-        nseg = offs.size - 1
-        for name, a in (("state", state), ("pos", pos)):
-            if a is not None and a.shape != (nseg,):
-                raise ValueError(f"{name}: nseg values")
-        if case is not None and case.shape != (nseg, self.case_words):
-            raise ValueError("case: nseg rows of case_words values")
-        grp = None
-        if stream_groups is not None:
-            grp = np.ascontiguousarray(stream_groups, dtype=np.uint32)
-            if grp.shape != (nseg,):
-                raise ValueError("stream_groups: nseg values")
-        u32p, u64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
-        cap = max(1024, len(arr) // 16)
-        while True:
-            ev = np.empty(cap, dtype=np.uint64)
-            total = ctypes.c_size_t(0)
-            st = None if state is None else state.copy()
-            ps = None if pos is None else pos.copy()
-            cs = None if case is None else case.copy()
-            head = (self.obj, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                    offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg)
-            tail = (None if grp is None else grp.ctypes.data_as(u32p), min_len, int(bool(all_matches)),
-                    ev.ctypes.data_as(u64p), cap, ctypes.byref(total))
-            if state is None:
-                rc = self.lib.pm_hip_read_batch_nocase(*head, *tail)
-            else:
-                rc = self.lib.pm_hip_read_flows_nocase(*head, st.ctypes.data_as(u32p),
-                                                       None if ps is None else ps.ctypes.data_as(u64p),
-                                                       None if cs is None or cs.size == 0 else cs.ctypes.data_as(u64p),
-                                                       *tail)
-            if rc != 0:
-                raise RuntimeError(self.lib.pm_hip_last_error().decode())
-            if total.value <= cap:
-                return ev[:total.value], st, ps, cs
-            cap = total.value
+        """_read_list for the nocase forms: (events u64 ascending, state_out,
+        pos_out, case_out -- None for the batched form)."""
+        return self._read_list("nocase", data, offsets, min_len, all_matches, stream_groups, state, pos, case)
 
     def read_batch_nocase(self, data, offsets, stream_groups=None, min_len=3, all_matches=True):
         """pm_hip_read_batch_nocase: read_batch_windows with the patterns'
@@ -939,10 +842,7 @@ class HipMatcher:
     def read_many_nocase(self, buffers, stream_groups=None, min_len=3, all_matches=True):
         """read_batch_nocase over a list of buffers, each a stream of its own:
         per buffer (positions inside it, codes)."""
-        offs = batch_offsets(buffers)
-        parts = [np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray)
-                 else np.ascontiguousarray(b, dtype=np.uint8).ravel() for b in buffers]
-        data = np.concatenate(parts) if parts else np.empty(0, np.uint8)
+        data, offs = _concat(buffers)
         pos, codes = self.read_batch_nocase(data, offs, stream_groups, min_len, all_matches)
         return _split_events(pos, codes, offs)
 
@@ -975,8 +875,7 @@ class HipMatcher:
         fn = {4: self.lib.pm_hip_scan_flows_device, 2: self.lib.pm_hip_scan_flows_device16}[out_width]
         rc = fn(self.obj, d_text_ptr, d_offsets_ptr, nseg, n, d_state_in_ptr, d_state_out_ptr, d_out_ptr, d_count_ptr,
                 stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def read_flows_gids(self, data, offsets, state=None):
         """pm_hip_read_flows_gid: (gids, state_out).  Stream j = data[offsets[j]:
@@ -998,8 +897,7 @@ class HipMatcher:
                                             offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg,
                                             st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
                                             out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
         return out, st
 
     def read_flows_codes(self, data, offsets, state=None):
@@ -1025,8 +923,7 @@ class HipMatcher:
                                         offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), nseg,
                                         st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_void_p)))
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
         return out[:len(arr)], st
 
     @property
@@ -1039,8 +936,7 @@ class HipMatcher:
         """pm_hip_gen_lines_device: the lines stream (random dictionary
         patterns back to back, '\\n' after each) of this object's patterns."""
         rc = self.lib.pm_hip_gen_lines_device(self.obj, d_dst_ptr, n, seed, stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def gen_lines(self, n, seed) -> np.ndarray:
         """The same bytes on the host (pm_gen_lines_host)."""
@@ -1052,15 +948,13 @@ class HipMatcher:
         """pm_hip_score_device: d_counts (5 u64) += success, partial,
         false_neg, false_pos, all_matches of algo ids against real ids."""
         rc = self.lib.pm_hip_score_device(self.obj, d_algo_ptr, d_real_ptr, n, d_counts_ptr, stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def pattern_counts_device(self, d_ids_ptr, n, d_hist_ptr, stream_ptr):
         """pm_hip_pattern_counts_device: d_hist (u64[n_patterns + 1], by gid)
         += occurrences of every pattern (suffix chains of the dense ids)."""
         rc = self.lib.pm_hip_pattern_counts_device(self.obj, d_ids_ptr, n, d_hist_ptr, stream_ptr)
-        if rc != 0:
-            raise RuntimeError(self.lib.pm_hip_last_error().decode())
+        self._check(rc)
 
     def hold_choice(self, launches):
         """pm_hip_hold_choice: keep the picked kernel for `launches` more
