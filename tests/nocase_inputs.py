@@ -169,11 +169,13 @@ def winners(pats):
     return {p: k for k, p in enumerate(pats)}
 
 
-def brute(pats, flags, streams, gid_of_index, min_len=1, groups=None, sgroups=None, windows=None, all_matches=True):
+def brute(pats, flags, streams, gid_of_index, min_len=1, groups=None, sgroups=None, windows=None, all_matches=True,
+          base=None):
     """Events of whole streams: an int64 array of rows (stream, position, gid,
     start of the match), sorted by (stream, position, gid), and a dict of counts
     {"nocase_case_differs", "rejected"}.  flags / groups / windows are per
-    pattern index; windows = (min_start, max_end) arrays."""
+    pattern index; windows = (min_start, max_end) arrays.  base[j]: the bytes
+    stream j had before its position 0 (the windows count them; Python ints)."""
     rows = []
     stats = {"nocase_case_differs": 0, "rejected": 0}
     win = winners(pats)
@@ -198,7 +200,7 @@ def brute(pats, flags, streams, gid_of_index, min_len=1, groups=None, sgroups=No
                     ok = False
                     stats["rejected"] += 1
                 if ok and windows is not None:
-                    E = e + 1
+                    E = (0 if base is None else int(base[j])) + e + 1
                     lo, hi = int(windows[0][k]), int(windows[1][k])
                     ok = E - L >= lo and (hi == INF or E <= hi)
                 if ok:

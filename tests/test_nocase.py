@@ -17,7 +17,8 @@ from test_batch import _dev, _stream
 from test_events import POISON64, Ev, _text_dev
 from test_flows import _state_values, _states
 from test_gpu_parity import _torch
-from test_nocase_cpu import _seam_dictionary, streams_of, tables_of
+from test_nocase_cpu import (SHIFT_LENGTHS, SHIFT_MIDDLES, _seam_dictionary, assert_shift_call, assert_two_word_shift,
+                             shift_calls, shift_flows, shift_pattern, streams_of, tables_of, two_word_shift_flows)
 
 pytestmark = pytest.mark.gpu
 
@@ -308,6 +309,49 @@ def test_flow_seams_pieces_equal_one_piece():
         assert np.array_equal(case[0], history_words(flow[:k + 1], 3)), k
     assert np.array_equal(np.array(got, np.uint64), one)
     m.free()
+
+
+def _shift_run(m, flows, W):
+    """shift_calls through the host form of the flow scan, the states,
+    positions and histories carried: the (flows, W) history words after each call."""
+    n = len(flows)
+    assert m.lib.pm_hip_gid_index(m.obj, 1) == 0  # one pattern: gid 1
+    st, pos, case, hists = np.zeros(n, np.uint32), np.zeros(n, np.uint64), np.zeros((n, W), np.uint64), []
+    for k, (text, offs) in enumerate(shift_calls(flows)):
+        ev, st, pos, case = m._read_nocase(text, offs, None, st, pos, case, 1, True)
+        assert_shift_call(k, flows, offs, ev, case, W)
+        hists.append(np.asarray(case).reshape(n, W).copy())
+    return hists
+
+
+@pytest.mark.parametrize("L", sorted(SHIFT_LENGTHS))
+def test_history_shifts_three_packets(L):
+    """nocase_history_kernel with a middle packet of 1, 63, 64, 65, 127 or 128
+    bytes between the two parts of a case-sensitive pattern: the old history
+    moves across a word boundary (old = back - len, word old >> 6) while the
+    pattern is open; a letter whose case was flipped in packet 1 or 2 must
+    still reject it at its last byte in packet 3."""
+    _torch()
+    p = shift_pattern(L)
+    m = build([p], "ac", [0])
+    try:
+        assert m.case_words == SHIFT_LENGTHS[L]
+        flows = shift_flows(p)
+        assert {len(f[1]) for f in flows} == {mid for mid in SHIFT_MIDDLES if mid <= L - 2}
+        _shift_run(m, flows, m.case_words)
+    finally:
+        m.free()
+
+
+def test_history_two_word_shift():
+    _torch()
+    p, flows = two_word_shift_flows()
+    m = build([p], "ac", [0])
+    try:
+        assert m.case_words == 4
+        assert_two_word_shift(flows, _shift_run(m, flows, 4))
+    finally:
+        m.free()
 
 
 def test_reductions_to_the_matches_calls():

@@ -299,6 +299,105 @@ def test_flow_seams_every_cut():
     assert np.array_equal(np.array(got, np.uint64), one)
 
 
+# ---- history shifts: a middle packet that moves old history across a word boundary --------
+SHIFT_LENGTHS = {64: 1, 65: 1, 66: 2, 129: 2, 130: 3, 200: 4}  # pattern length -> history words
+SHIFT_MIDDLES = (1, 63, 64, 65, 127, 128)
+SHIFT_CUTS = (1, 2, 63, 64, 65)
+
+
+def shift_pattern(L):
+    """A case-sensitive pattern of L letters of both cases."""
+    rng = np.random.default_rng(900 + L)
+    return bytes(rng.choice(np.frombuffer(b"aAbBcCdD", np.uint8), L))
+
+
+def shift_flows(p):
+    """The flows of one pattern: (packet 1, packet 2, packet 3, reported) with
+    "--" + p cut after the first cut and again a middle length later, the third
+    packet keeping at least a byte; after each unflipped flow its twins with
+    one letter's case flipped in packet 1 and in packet 2."""
+    L, flows = len(p), []
+    for mid in SHIFT_MIDDLES:
+        if mid > L - 2:
+            continue
+        for cut in sorted({min(c, L - mid - 1) for c in SHIFT_CUTS}):
+            assert cut >= 1 and cut + mid < L
+            for flip in (None, cut // 2, cut + mid // 2):
+                v = bytearray(p)
+                if flip is not None:
+                    v[flip] ^= 0x20
+                flows.append((b"--" + bytes(v[:cut]), bytes(v[cut:cut + mid]), bytes(v[cut + mid:]), flip is None))
+    return flows
+
+
+def shift_calls(flows):
+    """Three calls, every flow's k-th packet in call k: [(text, offsets)]."""
+    calls = []
+    for k in range(3):
+        parts = [f[k] for f in flows]
+        offs = np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.int64)
+        calls.append((np.frombuffer(b"".join(parts), np.uint8), offs))
+    return calls
+
+
+def assert_shift_call(k, flows, offs, ev, hist, W):
+    """Call k (0, 1, 2) of shift_calls: the pattern is reported at the last byte
+    of the unflipped flows' third packet and nowhere else, and every flow's
+    history is that of its bytes so far."""
+    want = [(int(offs[j + 1]) - 1) << 24 | 1 for j, f in enumerate(flows) if f[3]] if k == 2 else []
+    assert [int(e) for e in ev] == want, k
+    hist = np.asarray(hist).reshape(len(flows), W)
+    for j, f in enumerate(flows):
+        assert np.array_equal(hist[j], history_words(b"".join(f[:k + 1]), W)), (k, j)
+
+
+@pytest.mark.parametrize("L", sorted(SHIFT_LENGTHS))
+def test_history_shifts_three_packets(L):
+    p = shift_pattern(L)
+    tw = Twin([p], [0], pm.KIND_AC)
+    assert tw.W == SHIFT_LENGTHS[L]
+    flows = shift_flows(p)
+    assert len(flows) == 3 * sum(f[3] for f in flows)
+    assert {len(f[1]) for f in flows} == {m for m in SHIFT_MIDDLES if m <= L - 2}
+    st = pos = case = None
+    for k, (text, offs) in enumerate(shift_calls(flows)):
+        ev, st, pos, case = tw.scan(text, offs, state=st, pos=pos, case=case)
+        assert_shift_call(k, flows, offs, ev, case, tw.W)
+
+
+def two_word_shift_flows():
+    """A pattern of 200 bytes (4 history words); packet 2 is 128 bytes that are
+    no pattern text, with upper-case letters of their own.  Flow 0 then brings
+    the rest of the pattern: the head in its history completes nothing.  Flow
+    1 brings the whole pattern, found in the text alone."""
+    p = shift_pattern(200)
+    filler = bytes(b"xXyYzZ-"[(k * k) % 7] for k in range(128))
+    return p, [(b"--" + p[:72], filler, p[72:], False), (b"--" + p[:72], filler, p, True)]
+
+
+def assert_two_word_shift(flows, hists):
+    """hists[k]: the (flows, 4) history words after call k.  Call 2 moved
+    every word of call 1 up by two and filled the first two from its bytes."""
+    for j, f in enumerate(flows):
+        assert len(f[1]) == 128
+        assert np.array_equal(hists[1][j][2:], hists[0][j][:2]), j
+        assert np.array_equal(hists[1][j][:2], history_words(f[1], 2)), j
+        assert hists[0][j][0] != 0 and hists[0][j][1] != 0, j
+
+
+def test_history_two_word_shift():
+    p, flows = two_word_shift_flows()
+    tw = Twin([p], [0], pm.KIND_AC)
+    assert tw.W == 4
+    st = pos = case = None
+    hists = []
+    for k, (text, offs) in enumerate(shift_calls(flows)):
+        ev, st, pos, case = tw.scan(text, offs, state=st, pos=pos, case=case)
+        assert_shift_call(k, flows, offs, ev, case, 4)
+        hists.append(case.copy())
+    assert_two_word_shift(flows, hists)
+
+
 def test_reductions_and_tables():
     pats = fuzz_dictionary(2, n=120, long_cs=False)
     text = fuzz_text(pats, 2, 8192)
