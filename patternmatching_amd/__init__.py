@@ -30,6 +30,10 @@ interface:
                     nocase forms: a case-insensitivity flag per pattern,
                     Snort's nocase (HipMatcher.set_nocase, read_*_nocase /
                     scan_*_nocase_device, FlowTable.scan_nocase)
+    events_by_stream_host   any such list grouped by stream without a device
+                    (the host twin of HipMatcher.events_by_stream /
+                    events_by_stream_device / read_many_sets: per-stream
+                    ranges, optionally one event per stream and pattern)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401
@@ -39,6 +43,8 @@ from .matcher import (  # noqa: F401
     gen_stream,
     batch_offsets,
     unpack_events,
+    events_by_stream_host,
+    BY_STREAM_UNIQUE,
     parse_line,
     KIND_RT,
     KIND_AC,
@@ -46,4 +52,4 @@ from .matcher import (  # noqa: F401
 )
 
 __all__ = ["load", "Dictionary", "HipMatcher", "FlowTable", "gen_stream", "batch_offsets", "unpack_events", "parse_line",
-           "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]
+           "events_by_stream_host", "BY_STREAM_UNIQUE", "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]

@@ -32,6 +32,7 @@
 #include <thread>
 #include <vector>
 
+#include "pm_bystream.h"
 #include "pm_flatten.h"
 #include "pm_hip.h"
 #include "pm_host.h"
@@ -269,6 +270,15 @@ struct BatchStage {
     uint64_t* d_case_in = nullptr;
     uint64_t* d_case_out = nullptr;
     size_t cap_case = 0;
+    // the per-stream sets' host form (pm_hip_events_by_stream): a list in and out, cap_bs events of each,
+    // cap_bs_ptr stream_ptr values and cap_bs_scr bytes of the call's scratch
+    uint64_t* d_bs_in = nullptr;
+    uint64_t* d_bs_out = nullptr;
+    size_t cap_bs = 0;
+    int64_t* d_bs_ptr = nullptr;
+    size_t cap_bs_ptr = 0;
+    void* d_bs_scr = nullptr;
+    size_t cap_bs_scr = 0;
     hipStream_t s = nullptr;
 };
 // Per-pattern nocase (pm_hip_set_nocase): the images of the folded dictionary
@@ -1424,6 +1434,10 @@ void pm_hip_free(void* obj) {
     if (o->batch.d_pos_out) (void)hipFree(o->batch.d_pos_out);
     if (o->batch.d_case_in) (void)hipFree(o->batch.d_case_in);
     if (o->batch.d_case_out) (void)hipFree(o->batch.d_case_out);
+    if (o->batch.d_bs_in) (void)hipFree(o->batch.d_bs_in);
+    if (o->batch.d_bs_out) (void)hipFree(o->batch.d_bs_out);
+    if (o->batch.d_bs_ptr) (void)hipFree(o->batch.d_bs_ptr);
+    if (o->batch.d_bs_scr) (void)hipFree(o->batch.d_bs_scr);
     if (o->batch.s) (void)hipStreamDestroy(o->batch.s);
     free_pick(o->pick);
     for (PipeSlot& q : o->slot) {
@@ -2446,6 +2460,101 @@ int pm_hip_read_flows_nocase(void* obj, const uint8_t* buf, const int64_t* offse
                        buf, offsets, nseg, state, min_len, events, cap, nevents);
 }
 
+// ---- per-stream sets: a match list grouped by stream (pm_bystream.hip) -------
+// Every check, then the passes; nothing is written before all of them pass.
+int pm_hip_events_by_stream_device(void* obj, const uint64_t* d_events, uint64_t cap,
+                                   const unsigned long long* d_nevents, const int64_t* d_offsets, int64_t nseg,
+                                   uint32_t flags, uint64_t* d_out, uint64_t out_cap, int64_t* d_stream_ptr,
+                                   void* d_scratch, size_t scratch_bytes, void* hip_stream) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    bool ok = nseg >= 0 && nseg < PM_BS_MAX_NSEG && cap <= PM_BS_MAX_CAP && !(flags & ~PM_BY_STREAM_UNIQUE) &&
+              !misaligned(d_events, 8) && !misaligned(d_nevents, 8) && !misaligned(d_offsets, 8) &&
+              !misaligned(d_out, 8) && !misaligned(d_stream_ptr, 8) && !misaligned(d_scratch, 16) &&
+              !(d_out && d_out == d_events) && !(cap && !d_events) && !(out_cap && !d_out);
+    if (ok && nseg > 0)
+        ok = d_nevents && d_offsets && d_stream_ptr && d_scratch &&
+             scratch_bytes >= pm_by_stream_layout(cap, nseg, (flags & PM_BY_STREAM_UNIQUE) != 0).bytes;
+    if (!ok) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (events, nevents, offsets, out and stream_ptr non-NULL and 8-B aligned, scratch "
+                      "non-NULL and 16-B aligned, 0 <= nseg < 2^31, cap <= 2^40, flags 0 or PM_BY_STREAM_UNIQUE, out != "
+                      "events, scratch_bytes >= pm_hip_by_stream_scratch_bytes)");
+        return -2;
+    }
+    if (nseg == 0) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess) {
+        if (cap == 0)
+            e = hipMemsetAsync(d_stream_ptr, 0, ((size_t)nseg + 1) * sizeof(int64_t), (hipStream_t)hip_stream);
+        else
+            e = pm_launch_by_stream(d_events, cap, d_nevents, d_offsets, nseg, (flags & PM_BY_STREAM_UNIQUE) != 0, d_out,
+                                    out_cap, d_stream_ptr, d_scratch, o->num_cu, (hipStream_t)hip_stream);
+    }
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "by-stream launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    return 0;
+}
+
+// The host form: the list, its count and the offsets to the batch staging, the
+// device call with room for every event, stream_ptr back, then the events
+// kept; each stream's range is sorted here.
+int pm_hip_events_by_stream(void* obj, const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                            uint32_t flags, uint64_t* out, size_t out_cap, int64_t* stream_ptr) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    if ((nevents && !events) || (nseg && (!offsets || !stream_ptr)) || (out_cap && !out) ||
+        nseg >= (size_t)PM_BS_MAX_NSEG || nevents > PM_BS_MAX_CAP || (flags & ~PM_BY_STREAM_UNIQUE) ||
+        (out && out == events)) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (events, offsets, out and stream_ptr non-NULL, nseg < 2^31, nevents <= 2^40, flags "
+                      "0 or PM_BY_STREAM_UNIQUE, out != events)");
+        return -2;
+    }
+    if (nseg == 0) return 0;
+    if (nevents == 0) {
+        std::fill(stream_ptr, stream_ptr + nseg + 1, (int64_t)0);
+        return 0;
+    }
+    const bool unique = (flags & PM_BY_STREAM_UNIQUE) != 0;
+    PM_CHECK(hipSetDevice(o->device));
+    BatchStage& q = o->batch;
+    batch_stage_grow(q, 0, nseg);  // the stream and the offsets
+    stage_grow((void**)&q.d_bs_in, (void**)&q.d_bs_out, sizeof(uint64_t), q.cap_bs, nevents);
+    stage_grow((void**)&q.d_bs_ptr, nullptr, sizeof(int64_t), q.cap_bs_ptr, nseg + 2);  // + the list's cursor
+    const size_t need = pm_by_stream_layout(nevents, (int64_t)nseg, unique).bytes;
+    stage_grow(&q.d_bs_scr, nullptr, 1, q.cap_bs_scr, need);
+    unsigned long long* d_cursor = reinterpret_cast<unsigned long long*>(q.d_bs_ptr + nseg + 1);
+    const unsigned long long cursor = nevents;
+    serve_stop(o);  // a device launch wants the whole device
+    PM_CHECK(hipMemcpyAsync(q.d_bs_in, events, nevents * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(d_cursor, &cursor, sizeof(cursor), hipMemcpyHostToDevice, q.s));
+    const hipError_t e = pm_launch_by_stream(q.d_bs_in, nevents, d_cursor, q.d_offs, (int64_t)nseg, unique, q.d_bs_out,
+                                             nevents, q.d_bs_ptr, q.d_bs_scr, o->num_cu, q.s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(q.s);
+        std::snprintf(g_err, sizeof(g_err), "by-stream launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    std::vector<int64_t> ptr(nseg + 1);
+    PM_CHECK(hipMemcpyAsync(ptr.data(), q.d_bs_ptr, ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, q.s));
+    PM_CHECK(hipStreamSynchronize(q.s));
+    const size_t kept = (size_t)ptr[nseg];  // <= nevents: every kept event was stored
+    std::vector<uint64_t> ev(kept);
+    if (kept) PM_CHECK(hipMemcpyAsync(ev.data(), q.d_bs_out, kept * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    PM_CHECK(hipStreamSynchronize(q.s));
+    par_range(nseg, (size_t)1 << 12, [&](size_t lo, size_t hi) {
+        for (size_t j = lo; j < hi; ++j) std::sort(ev.begin() + ptr[j], ev.begin() + ptr[j + 1]);
+    });
+    std::memcpy(stream_ptr, ptr.data(), ptr.size() * sizeof(int64_t));
+    if (out_cap && kept) std::memcpy(out, ev.data(), std::min(out_cap, kept) * sizeof(uint64_t));
+    return 0;
+}
+
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,
                         unsigned long long* d_counts, void* hip_stream) {
     PmHip* o = as(obj);
@@ -2505,6 +2614,9 @@ size_t pm_hip_scratch_bytes(void* obj) {
     if (o->batch.d_grp) b += o->batch.cap_grp * sizeof(uint32_t);
     if (o->batch.d_pos_in) b += 2 * o->batch.cap_pos * sizeof(uint64_t);
     if (o->batch.d_case_in) b += 2 * o->batch.cap_case * sizeof(uint64_t);
+    if (o->batch.d_bs_in) b += 2 * o->batch.cap_bs * sizeof(uint64_t);
+    if (o->batch.d_bs_ptr) b += o->batch.cap_bs_ptr * sizeof(int64_t);
+    if (o->batch.d_bs_scr) b += o->batch.cap_bs_scr;
     return b;
 }
 

@@ -156,6 +156,34 @@ def _split_events(pos, codes, offs):
     return [(pos[cut[j]:cut[j + 1]] - offs[j], codes[cut[j]:cut[j + 1]]) for j in range(len(offs) - 1)]
 
 
+BY_STREAM_UNIQUE = 1  # PM_BY_STREAM_UNIQUE: one event per (stream, pattern), at its first position
+
+
+def _by_stream_host_args(events, offsets, out_cap):
+    """The host arrays of a per-stream-sets call: (events u64, offsets int64,
+    out u64 of out_cap slots -- every event when None --, stream_ptr int64)."""
+    ev = np.ascontiguousarray(events, dtype=np.uint64).ravel()
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offs.ndim != 1 or offs.size < 1:
+        raise ValueError("offsets: nseg + 1 values")
+    out = np.empty(len(ev) if out_cap is None else out_cap, dtype=np.uint64)
+    return ev, offs, out, np.zeros(offs.size, dtype=np.int64)
+
+
+def events_by_stream_host(events, offsets, unique=True, out_cap=None):
+    """pm_flat_events_by_stream, the host twin of HipMatcher.events_by_stream
+    (no matcher, no device): (stream_ptr, events) with each stream's range
+    ascending; the events array holds min(out_cap, stream_ptr[-1]) of them."""
+    ev, offs, out, ptr = _by_stream_host_args(events, offsets, out_cap)
+    u64p, i64p = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64)
+    rc = load().pm_flat_events_by_stream(ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p), offs.size - 1,
+                                         BY_STREAM_UNIQUE if unique else 0, out.ctypes.data_as(u64p), len(out),
+                                         ptr.ctypes.data_as(i64p))
+    if rc != 0:
+        raise ValueError(f"pm_flat_events_by_stream: bad arguments ({rc})")
+    return ptr, out[:min(len(out), int(ptr[-1]))]
+
+
 class FlowTable:
     """The carried states of many live flows over one matcher (ac / auto
     kinds): a dict of flow key -> flow state, and one flow call
@@ -626,6 +654,53 @@ class HipMatcher:
         ev, st = self._read_events(data, offsets, st, min_len, all_matches=True)
         pos, gids = unpack_events(ev)
         return pos, self._codes[gids], st
+
+    # --- per-stream sets: a match list grouped by stream ---------------------
+    def by_stream_scratch_bytes(self, cap, nseg, unique=True):
+        """pm_hip_by_stream_scratch_bytes: the device scratch, in bytes, that
+        events_by_stream_device needs for a list of cap slots over nseg streams."""
+        b = self.lib.pm_hip_by_stream_scratch_bytes(cap, nseg, BY_STREAM_UNIQUE if unique else 0)
+        if b == ctypes.c_size_t(-1).value:
+            raise ValueError("by_stream_scratch_bytes: cap <= 2^40, 0 <= nseg < 2^31")
+        return b
+
+    def events_by_stream_device(self, d_events_ptr, cap, d_nevents_ptr, d_offsets_ptr, nseg, flags, d_out_ptr, out_cap,
+                                d_stream_ptr_ptr, d_scratch_ptr, scratch_bytes, stream_ptr):
+        """pm_hip_events_by_stream_device: the list a scan left in
+        d_events_ptr[0, cap) behind the device cursor d_nevents_ptr, grouped by
+        the scan's streams: stream j's events to d_out_ptr[ptr[j] .. ptr[j+1])
+        with ptr = the nseg + 1 int64 at d_stream_ptr_ptr; flags
+        BY_STREAM_UNIQUE keeps one event per (stream, pattern), at its first
+        position.  Enqueued on stream_ptr, no synchronize."""
+        rc = self.lib.pm_hip_events_by_stream_device(self.obj, d_events_ptr, cap, d_nevents_ptr, d_offsets_ptr, nseg,
+                                                     flags, d_out_ptr, out_cap, d_stream_ptr_ptr, d_scratch_ptr,
+                                                     scratch_bytes, stream_ptr)
+        self._check(rc)
+
+    def events_by_stream(self, events, offsets, unique=True):
+        """pm_hip_events_by_stream: host arrays through the device call:
+        (stream_ptr int64 of nseg + 1, events u64), stream j's events
+        events[ptr[j]:ptr[j+1]] ascending; unique: one per (stream, pattern),
+        at the pattern's first position in the stream."""
+        ev, offs, out, ptr = _by_stream_host_args(events, offsets, None)
+        u64p, i64p = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64)
+        rc = self.lib.pm_hip_events_by_stream(self.obj, ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p),
+                                              offs.size - 1, BY_STREAM_UNIQUE if unique else 0,
+                                              out.ctypes.data_as(u64p), len(out), ptr.ctypes.data_as(i64p))
+        self._check(rc)
+        return ptr, out[:int(ptr[-1])]
+
+    def read_many_sets(self, buffers, min_len=3, all_matches=True):
+        """One batch list call over a list of bytes-like streams, then
+        events_by_stream: per stream, in order, (first positions inside the
+        stream, codes) of the distinct patterns of at least min_len bytes that
+        end in it (all_matches False: of the longest pattern per position)."""
+        data, offs = _concat(buffers)
+        ev, _ = self._read_events(data, offs, None, min_len, all_matches=all_matches)
+        ptr, ev = self.events_by_stream(ev, offs, unique=True)
+        pos, gids = unpack_events(ev)
+        codes = self._codes[gids]
+        return [(pos[ptr[j]:ptr[j + 1]] - offs[j], codes[ptr[j]:ptr[j + 1]]) for j in range(len(buffers))]
 
     # --- pattern groups: a group mask per pattern and one per stream --------
     def set_groups(self, masks):
