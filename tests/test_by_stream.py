@@ -13,11 +13,13 @@ import pytest
 
 import patternmatching_amd as pm
 from batch_inputs import input_t
+from by_stream_inputs import (distinct_keys, first_difference, first_range_difference, mixed_offsets, pack, scan_like,
+                              scattered)
 from flow_inputs import input_f
 from test_batch import _dev, _stream
 from test_events import GUARD, POISON64, Ev, _text_dev
 from oracle_lib import dict_paths
-from test_gpu_parity import _torch, matcher
+from test_gpu_parity import SHIP, _torch, fresh_matcher, matcher
 
 pytestmark = pytest.mark.gpu
 
@@ -40,10 +42,6 @@ def own_matcher():
         m.compile()
         _own["m"] = m
     return _own["m"]
-
-
-def pack(pos, gid):
-    return (np.asarray(pos, dtype=np.uint64) << np.uint64(24)) | np.asarray(gid, dtype=np.uint64)
 
 
 def _i64(torch, n, value):
@@ -96,11 +94,21 @@ def _sorted_ranges(ptr, out):
     return body[np.lexsort((body, seg))]
 
 
-def _run(events, offs, cap=None, cursor=None, out_cap=None, flags=(0, 1), key="et", kind="rt"):
+def _assert_equals_twin(ptr, out, exp_ptr, exp_ev, what):
+    """stream_ptr and the sorted ranges against the twin's; a difference names
+    the first differing stream and its expected and observed counts."""
+    diff = first_difference(ptr, exp_ptr)
+    assert not diff, f"{what}: stream_ptr: {diff}"
+    assert ptr[0] == 0 and ptr[-1] == exp_ptr[-1], what
+    diff = first_range_difference(ptr, _sorted_ranges(ptr, out), exp_ev)
+    assert not diff, f"{what}: {diff}"
+
+
+def _run(events, offs, cap=None, cursor=None, out_cap=None, flags=(0, 1), key="et", kind="rt", m=None):
     """The device call on a hand-made list against the twin on the events it
-    has to use, for each flag value."""
+    has to use, for each flag value (m: an object of the caller's own)."""
     torch = _torch()
-    m = matcher(key, kind)
+    m = matcher(key, kind) if m is None else m
     events = np.ascontiguousarray(events, dtype=np.uint64)
     offs = np.ascontiguousarray(offs, dtype=np.int64)
     nseg = len(offs) - 1
@@ -118,8 +126,7 @@ def _run(events, offs, cap=None, cursor=None, out_cap=None, flags=(0, 1), key="e
         ptr, out = o.result()
         ev.assert_guard(cap)
         assert ev.total() == cursor
-        assert np.array_equal(ptr, exp_ptr), f"flags {f}: stream_ptr differs"
-        assert np.array_equal(_sorted_ranges(ptr, out), exp_ev), f"flags {f}: events differ"
+        _assert_equals_twin(ptr, out, exp_ptr, exp_ev, f"flags {f}")
         assert np.all(out[ptr[-1]:] == POISON64), f"flags {f}: a slot past the kept events was written"
         res[f] = (ptr, exp_ev)
     return res
@@ -443,3 +450,184 @@ def test_return_codes_and_nothing_written():
         assert b"bad arguments" in lib.pm_hip_last_error(), k
     assert np.all(out == POISON64) and np.all(ptr == PTR_POISON)
     assert lib.pm_hip_by_stream_scratch_bytes(1, -1, 0) == NONE
+
+
+# ---- 9. past one grid, far positions, an empty list, the wave leaders --------------------------
+_grid = {}
+
+
+def _grid_inputs():
+    """(lanes of one full grid, stream offsets, a scan_like list of two such
+    grids and a wave, the generator behind it); made once."""
+    if not _grid:
+        lanes = 8 * 256 * _torch().cuda.get_device_properties(0).multi_processor_count  # bs_grid's cap
+        rng = np.random.default_rng(11)
+        offs = mixed_offsets(rng)
+        assert {0, 1} <= set(np.diff(offs).tolist()) and np.diff(offs).max() >= 100000
+        _grid["in"] = (lanes, offs, scan_like(2 * lanes + 64, offs, np.arange(1, 9), rng), rng)
+    return _grid["in"]
+
+
+@pytest.mark.parametrize("which", ["scan_like", "scattered", "distinct_keys", "a_wave_past_a_turn",
+                                   "a_wave_short_of_a_turn"])
+def test_more_events_than_one_grid(which):
+    """A launch is capped at 8 workgroups of 256 lanes per CU (bs_grid): a list
+    of two full turns of that grid and a ragged third, so that the grid-stride
+    loops of all four event and table kernels turn again -- a wave meets a
+    stream's count twice, the rounded tail of invalid lanes sits in the last
+    turn, and UNIQUE's table has 2^21 slots or more (distinct_keys: exactly
+    half full).  Streams of 0, 1, about 1,500 and one of about 100,000
+    positions; gids 1..8, so nearly every event is a duplicate.  Then the
+    scan_like list ending one wave past and one wave short of a whole turn.
+    (One parameter per list: together they took 1.5 s, most of it the twin's.)"""
+    lanes, offs, like, rng = _grid_inputs()
+    n = 2 * lanes + 37
+    if which == "scan_like":
+        res = _run(like[:n], offs)
+        assert res[0][0][-1] > n - n // 100 and res[1][0][-1] <= 8 * (len(offs) - 1)
+    elif which == "scattered":
+        _run(scattered(n, offs, np.arange(1, 9), rng), offs)
+    elif which == "distinct_keys":
+        pow2 = 1 << (n - 1).bit_length()
+        assert pm.load().pm_hip_by_stream_scratch_bytes(pow2, 1, 1) >= 20 * max(2 * pow2, 1 << 21)
+        res = _run(distinct_keys(pow2, offs, rng), offs)
+        assert res[1][0][-1] == res[0][0][-1] == pow2  # nothing outside a stream, no key twice
+    elif which == "a_wave_past_a_turn":
+        _run(like, offs)
+    else:
+        _run(like[:2 * lanes - 64], offs)
+
+
+def test_positions_up_to_2_40():
+    """test_positions_above_2_32 at the top of the position field: the last
+    stream ends at 2^40 and holds an event at 2^40 - 1, of a gid of its own so
+    that UNIQUE keeps it too; the other gids include the largest."""
+    top, gid_max = 1 << 40, (1 << 24) - 1
+    base = top - 9100
+    offs = base + np.array([0, 1000, 1000, 5000, 5001, 9100], dtype=np.int64)
+    rng = np.random.default_rng(12)
+    pos = np.append(base + rng.integers(-50, 9100, size=5000), top - 1)
+    gid = np.append(rng.choice([1, 2, gid_max], size=5000), gid_max - 1)
+    res = _run(pack(pos, gid), offs)
+    assert 0 < res[0][0][-1] < 5001
+    for f in (0, 1):
+        kept_pos, kept_gid = pm.unpack_events(res[f][1])
+        assert int(kept_pos.max()) == top - 1 and int(kept_gid.max()) == gid_max
+
+
+def test_cursor_zero_with_room():
+    """A list of 2,000 poisoned slots behind a cursor of 0: nothing is read
+    (as an event the poison lies inside the last stream), stream_ptr is all
+    zero and out untouched."""
+    res = _run(np.empty(0, np.uint64), [0, 100, 250, 1 << 40], cap=2000, cursor=0)
+    for f in (0, 1):
+        assert res[f][0].tolist() == [0, 0, 0, 0] and len(res[f][1]) == 0  # (_run: every out slot is poison)
+
+
+def test_wave_leaders():
+    """Four waves (64 events at aligned indices) whose lane 0, the lane
+    bs_stream_of searches for once per wave, is 1. below offsets[0]; 2. at
+    offsets[nseg]; 3. in the last stream with every other lane in stream 0 (far
+    below the leader: the search from the start); 4. in an interior stream with
+    the other lanes alternating between the stream before and the one after."""
+    offs = np.array([100, 110, 110, 130, 150, 170, 200], dtype=np.int64)  # stream 1 is empty
+    lane = np.arange(64)
+    w1 = np.where(lane == 0, 99, 110 + lane % 20)  # 63 events in stream 2
+    w2 = np.where(lane == 0, 200, np.where(lane < 32, 250, 130 + lane % 20))  # 32 in stream 3, 32 outside
+    w3 = np.where(lane == 0, 199, 100 + lane % 10)  # 1 in stream 5, 63 in stream 0
+    w4 = np.where(lane == 0, 140, np.where(lane % 2 == 1, 129 - lane % 20, 150 + lane % 20))  # 1 / 32 / 31 in 3 / 2 / 4
+    pos = np.concatenate([w1, w2, w3, w4])
+    res = _run(pack(pos, 1 + np.tile(lane, 4) % 3), offs)
+    assert res[0][0].tolist() == [0, 63, 63, 158, 191, 222, 223]
+    assert res[1][0].tolist() == [0, 3, 3, 6, 9, 12, 13]
+
+
+# ---- 10. captured behind a scan, and between served read_block calls ---------------------------
+def test_captured_behind_a_scan_and_replayed():
+    """scan_batch_matches_device, the by-stream call with flags 0 and, on
+    outputs and scratch of its own, with flags 1, captured as one chain on a
+    side stream and replayed three times, text B copied over the text in place
+    before the second: every replay groups that replay's list; the scratch and
+    stream_ptr are not reset between replays, so what one leaves behind (the
+    counts, the table) would show in the next."""
+    torch = _torch()
+    text, offs, _ = input_t("et")
+    other = np.ascontiguousarray(text[::-1])
+    n, nseg = len(text), len(offs) - 1
+    m = fresh_matcher("et", "rt")  # no read_block call: no resident server to stop inside the capture
+    try:
+        d_text, d_offs = _text_dev(torch, text), _dev(torch, offs)
+        ev = Ev(torch, 4 * n)
+        outs = [Out(torch, m, ev.cap, nseg, flags, ev.cap) for flags in (0, 1)]
+        # the scan alone once outside the capture: what it sets up on its first launch is set up
+        m.scan_batch_matches_device(d_text.data_ptr(), d_offs.data_ptr(), nseg, n, 3, ev.buf.data_ptr(), ev.cap,
+                                    ev.nev.data_ptr(), _stream(torch))
+        torch.cuda.synchronize()
+        st = torch.cuda.Stream()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=st):
+            m.scan_batch_matches_device(d_text.data_ptr(), d_offs.data_ptr(), nseg, n, 3, ev.buf.data_ptr(), ev.cap,
+                                        ev.nev.data_ptr(), st.cuda_stream)
+            for flags, o in enumerate(outs):
+                m.events_by_stream_device(ev.buf.data_ptr(), ev.cap, ev.nev.data_ptr(), d_offs.data_ptr(), nseg, flags,
+                                          o.out.data_ptr(), o.out_cap, o.ptr.data_ptr(), o.scratch.data_ptr(), o.bytes,
+                                          st.cuda_stream)
+        torch.cuda.synchronize()
+        seen = []
+        for replay in range(3):
+            if replay == 1:
+                d_text[:n].copy_(torch.from_numpy(other))
+            ev.nev.zero_()
+            for o in outs:
+                o.out[:o.out_cap].fill_(POISON64 - (1 << 64))
+            torch.cuda.synchronize()
+            gr.replay()
+            torch.cuda.synchronize()
+            total = ev.total()
+            assert 0 < total <= ev.cap
+            lst = ev.slots()[:total]
+            seen.append([])
+            for flags, o in enumerate(outs):
+                ptr, out = o.result()
+                exp_ptr, exp_ev = pm.events_by_stream_host(lst, offs, unique=bool(flags))
+                _assert_equals_twin(ptr, out, exp_ptr, exp_ev, f"replay {replay}, flags {flags}")
+                assert np.all(out[ptr[-1]:] == POISON64)
+                seen[-1].append((ptr.copy(), exp_ev))
+            assert seen[-1][0][0][-1] == total and seen[-1][1][0][-1] < total
+        for flags in (0, 1):
+            assert not np.array_equal(seen[0][flags][0], seen[1][flags][0])  # another text, another grouping
+            assert np.array_equal(seen[1][flags][0], seen[2][flags][0])
+            assert np.array_equal(seen[1][flags][1], seen[2][flags][1])
+    finally:
+        m.free()
+
+
+def test_call_between_served_read_blocks():
+    """Small read_block calls of an rt object go to its resident server grid;
+    a by-stream device call after every third asks the grid to leave the
+    device first, like every device launch, and the next small call launches
+    it again: the gids equal one large call's, every by-stream result the
+    twin's."""
+    m = fresh_matcher("snort", "rt")
+    try:
+        sizes = [100 << 10] * 9
+        text = np.tile(SHIP, 1 + sum(sizes) // len(SHIP))[:sum(sizes)]
+        cuts = np.cumsum([0] + sizes)
+        m.reset()
+        whole = m.read_block_gids(text)  # > 256 Ki positions: the pipeline, not the server
+        m.reset()
+        s0 = m.serve_stats()
+        rng = np.random.default_rng(13)
+        offs = np.concatenate([[3], 3 + np.cumsum(rng.integers(0, 30, size=300))]).astype(np.int64)
+        parts = []
+        for k, (a, b) in enumerate(zip(cuts[:-1], cuts[1:])):
+            parts.append(m.read_block_gids(text[a:b]))
+            if k % 3 == 2:
+                events = pack(rng.integers(0, offs[-1] + 10, size=3000), rng.integers(1, 6, size=3000))
+                _run(events, offs, m=m)
+        assert np.array_equal(np.concatenate(parts), whole)
+        s1 = m.serve_stats()
+        assert s1["calls"] - s0["calls"] == len(sizes)
+        assert s1["launches"] - s0["launches"] >= 3  # the first call, and the call after each stop
+    finally:
+        m.free()

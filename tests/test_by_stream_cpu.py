@@ -9,39 +9,12 @@ import numpy as np
 import pytest
 
 import patternmatching_amd as pm
+from by_stream_inputs import GID_MAX, pack, reference
 
 U64P = ctypes.POINTER(ctypes.c_uint64)
 I64P = ctypes.POINTER(ctypes.c_int64)
-GID_MAX = (1 << 24) - 1
 POISON64 = 0xA5A5A5A5A5A5A5A5
 PTR_POISON = -0x5A5A5A5A5A5A5A5B
-
-
-def pack(pos, gid):
-    return (np.asarray(pos, dtype=np.uint64) << np.uint64(24)) | np.asarray(gid, dtype=np.uint64)
-
-
-def reference(events, offsets, unique):
-    """(stream_ptr, events): each stream's range ascending.  The stream of a
-    position is the first offset above it, minus one; UNIQUE keeps the
-    smallest position of each (stream, gid)."""
-    events = np.asarray(events, dtype=np.uint64)
-    offs = np.asarray(offsets, dtype=np.int64)
-    nseg = len(offs) - 1
-    pos = (events >> np.uint64(24)).astype(np.int64)
-    j = np.searchsorted(offs, pos, side="right") - 1
-    keep = (j >= 0) & (j < nseg)
-    j, ev = j[keep], events[keep]
-    if unique:
-        first = {}
-        for s, e in zip(j.tolist(), ev.tolist()):
-            k = (s, e & GID_MAX)
-            first[k] = min(first.get(k, e), e)  # equal gid: the smaller event is the smaller position
-        j = np.array([k[0] for k in first], dtype=np.int64)
-        ev = np.array(list(first.values()), dtype=np.uint64)
-    order = np.lexsort((ev, j))
-    ptr = np.searchsorted(j[order], np.arange(nseg + 1), side="left").astype(np.int64)
-    return ptr, ev[order]
 
 
 def twin_raw(events, offsets, flags, out_cap, guard=8):
