@@ -642,6 +642,131 @@ int pm_hip_events_by_stream(void* obj, const uint64_t* events, size_t nevents, c
 int pm_flat_events_by_stream(const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
                              uint32_t flags, uint64_t* out, size_t out_cap, int64_t* stream_ptr);
 
+/*
+ * Rules: which multi-pattern rules fire in each stream, on the device.  A
+ * rule engine's rule is several patterns, some of them negated (Snort's
+ * content: and content:!, Hyperscan's logical combinations).  One call takes
+ * the list a scan left behind and gives, per stream, the rules that fired.
+ * A rule is a list of 1 to 64 terms; a term is a pattern gid (the number the
+ * events carry in their low 24 bits), positive or negated.  Over one stream
+ * let S be the set of gids with at least one used event inside the stream.
+ * The rule fires in the stream iff every positive term's gid is in S and no
+ * negated term's gid is.  The position of the hit is the largest of the first
+ * (smallest) positions its positive terms have in the stream: the byte at
+ * which the conjunction became true; negations do not move it.  Positions are
+ * buffer-global, as in the events.  A hit is position << 24 | rule, rule the
+ * rule's 0-based index: the events' own format.  The hits are a pure function
+ * of the used events, the offsets and the rules: duplicate events, events
+ * outside every stream, the order of the list and the choice of anchors
+ * change nothing.
+ * Rules see only what the list holds.  For exact rule semantics scan
+ *   - with an all-matches form (all != 0; pm_hip_scan_*_matches_device is
+ *     one): the longest-match forms drop the patterns that end at a position
+ *     beside a longer one;
+ *   - at a min_len no larger than the shortest term (pm_hip_rules_min_len):
+ *     a scan leaves out every pattern shorter than its min_len;
+ *   - with a cap that holds the whole list: an overflowed list lacks events,
+ *     so positive terms may miss and negated ones pass.
+ * Flows are out of scope: a rule is evaluated over the streams of one call,
+ * and no set is carried from one packet of a flow to the next.
+ * pm_hip_set_rules: the rules in CSR form.  term_ptr has nrules + 1 values,
+ * starts at 0 and does not decrease; rule r's terms are terms[term_ptr[r] ..
+ * term_ptr[r+1]).  A term holds the gid in bits 0-23; PM_RULE_NEGATED (bit
+ * 31) marks a negated term; PM_RULE_FAST (bit 30) marks the rule's anchor,
+ * the caller's fast_pattern: the term at whose (stream, gid) the rule is
+ * verified.  Without one the anchor is the positive term with the longest
+ * pattern, ties going to the smaller gid.  After compile() only: -1 before.
+ * -2, with one message naming every constraint, for: a NULL array; nrules 0
+ * or above 2^24; a rule with 0 or more than 64 terms; a rule with no positive
+ * term; a gid that names no pattern (pm_hip_pattern_len(obj, gid) == 0); a gid
+ * twice in one rule; bits besides the three fields; two PM_RULE_FAST terms in
+ * one rule or one on a negated term.  Nothing changes on an error.  The call
+ * builds the device tables (an inverted index gid -> the rules anchored at
+ * it, and each rule's other terms, positive ones first), counted in
+ * pm_hip_table_bytes.  A later call replaces them after a device synchronize,
+ * like pm_hip_set_windows: no rules call may be in flight.  compile() and the
+ * compiled-image cache do not see rules, and an object that never calls this
+ * behaves exactly as before.
+ * pm_hip_rule_count: the rules set (0 before).  pm_hip_rules_min_len: the
+ * length of the shortest pattern any term names (0 before pm_hip_set_rules).
+ * pm_hip_rules_by_stream_device: d_events, cap, d_nevents, d_offsets and nseg
+ * are exactly those of pm_hip_events_by_stream_device: the raw list behind
+ * its device cursor, of which min(*d_nevents, cap) events are used, the
+ * cursor read on the device, so the call may be enqueued right behind the
+ * scan with no synchronize between.  Output: d_rule_ptr gets nseg + 1 int64
+ * values; stream j's hits are d_hits[ptr[j] .. ptr[j+1]), in unspecified
+ * order inside a range; ptr[0] == 0, ptr[nseg] = the hits.  d_rule_ptr is
+ * complete and exact whatever hits_cap is; a hit whose slot is >= hits_cap is
+ * not stored and nothing at or past d_hits[hits_cap] is written.  The number
+ * of hits is NOT bounded by cap (one event can anchor many rules), so the
+ * exact d_rule_ptr[nseg] is what a caller sizes a retry from.  The call
+ * allocates nothing, runs asynchronously on hip_stream with no host
+ * synchronize inside (it may be captured), and asks the resident read_block
+ * server to leave the device first, like every device launch.  Scratch comes
+ * from the caller, 16-byte aligned, pm_hip_rules_scratch_bytes(cap, nseg)
+ * bytes exactly:
+ *     16 T + r16(8 nseg) + r16(8 ceil(nseg / 1024))
+ * T = the power of two >= max(2 cap, 64), the by-stream call's table (a key
+ * and a position per slot), r16 rounding up to 16 (the streams' counts and
+ * the scan's block sums follow the table); (size_t)-1 for arguments the call
+ * would reject.
+ * Returns 0; -1 before compile(); -2 bad arguments, one message for all of:
+ * a NULL pointer (d_events with cap > 0, d_hits with hits_cap > 0, d_nevents,
+ * d_offsets, d_rule_ptr, d_scratch) or a misaligned one (8 bytes; d_scratch
+ * 16), nseg < 0 or >= 2^31, cap > 2^40, d_hits == d_events, scratch_bytes too
+ * small; -10 pm_hip_set_rules was not called; -3 launch error.  Nothing is
+ * launched or written when a check fails.  nseg == 0: returns 0 and launches
+ * nothing.  cap == 0 with nseg > 0: an all-zero d_rule_ptr.
+ * Memory safety does not depend on the data: stream indices are clamped into
+ * [0, nseg), a gid above the last pattern anchors nothing, probe indices are
+ * masked by the table size; garbage offsets or events give unspecified hits,
+ * never an access outside the arrays named here.
+ * pm_hip_rules_by_stream: the host form.  events (nevents of them), offsets
+ * and the outputs are HOST arrays; it stages them on the object's batch
+ * stream (staging counted in pm_hip_scratch_bytes), runs the device call (a
+ * second time where its hits array was too short), sorts each stream's range
+ * ascending and hands over rule_ptr and the first min(hits_cap, total) hits.
+ * -1, -2 (a NULL array, nseg >= 2^31, nevents > 2^40, hits == events), -10 and
+ * -3 as above.
+ * pm_flat_rule_tables, pm_flat_rules_by_stream: the host alone, no handle and
+ * no device; they set no message.  pm_flat_rule_tables runs every check of
+ * pm_hip_set_rules (pattern_len: npat + 1 lengths by gid, [0] == 0; a gid
+ * above npat names no pattern), picks each rule's anchor and returns the
+ * inverted index in CSR form: anchor_ptr_out[npat + 2] by gid,
+ * anchor_rules_out[nrules] the rules anchored at each gid, ascending inside a
+ * gid's range, anchor_term_out[nrules] the index in terms of each rule's
+ * anchor; 0, or -2 with nothing written.  pm_flat_rules_by_stream is the twin
+ * of the device call over host arrays, each range sorted ascending; it needs
+ * no anchors and no dictionary (it checks everything about the rules but
+ * whether a gid names a pattern); 0, or -2.
+ * Measured (64 MiB, all-matches lists at min_len 3, 10,000 synthetic rules of
+ * 2-4 positive terms, a fifth with a negated one; profiles/rules/): the call
+ * alone takes 0.045-0.053 ms on random ASCII (51-70 thousand events) and
+ * 1.9-2.6 ms on the lines stream (15-17 million events): 0.07-0.16x and
+ * 0.40-1.14x the scan that made its list (above it only behind the flow scan
+ * on lines), 0.68-1.57x the PM_BY_STREAM_UNIQUE call on the same list, and
+ * 0.0028-0.0137x the UNIQUE sets copied to the host and walked by
+ * pm_flat_rules_by_stream on one thread.  5,000 rules more on one frequent
+ * anchor: 0.5-0.7 ms on ASCII, 2.3-12 ms on lines ("Rules").
+ */
+#define PM_RULE_NEGATED 0x80000000u
+#define PM_RULE_FAST 0x40000000u
+int pm_hip_set_rules(void* obj, const uint32_t* term_ptr, const uint32_t* terms, size_t nrules);
+size_t pm_hip_rule_count(void* obj);
+uint32_t pm_hip_rules_min_len(void* obj);
+size_t pm_hip_rules_scratch_bytes(uint64_t cap, int64_t nseg);
+int pm_hip_rules_by_stream_device(void* obj, const uint64_t* d_events, uint64_t cap,
+                                  const unsigned long long* d_nevents, const int64_t* d_offsets, int64_t nseg,
+                                  uint64_t* d_hits, uint64_t hits_cap, int64_t* d_rule_ptr, void* d_scratch,
+                                  size_t scratch_bytes, void* hip_stream);
+int pm_hip_rules_by_stream(void* obj, const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                           uint64_t* hits, size_t hits_cap, int64_t* rule_ptr);
+int pm_flat_rule_tables(const uint32_t* term_ptr, const uint32_t* terms, size_t nrules, const uint32_t* pattern_len,
+                        size_t npat, uint32_t* anchor_ptr_out, uint32_t* anchor_rules_out, uint32_t* anchor_term_out);
+int pm_flat_rules_by_stream(const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                            const uint32_t* term_ptr, const uint32_t* terms, size_t nrules, uint64_t* hits,
+                            size_t hits_cap, int64_t* rule_ptr);
+
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,
  * PatternsTree.c:485-494): per position, equal -> success; d_algo's pattern

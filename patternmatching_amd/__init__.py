@@ -34,6 +34,10 @@ interface:
                     (the host twin of HipMatcher.events_by_stream /
                     events_by_stream_device / read_many_sets: per-stream
                     ranges, optionally one event per stream and pattern)
+    rules_by_stream_host    which multi-pattern rules (positive and negated
+                    terms, pack_rules) fire in each stream of such a list,
+                    without a device (the host twin of HipMatcher.set_rules /
+                    rules_by_stream / rules_by_stream_device / read_many_rules)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401
@@ -45,6 +49,10 @@ from .matcher import (  # noqa: F401
     unpack_events,
     events_by_stream_host,
     BY_STREAM_UNIQUE,
+    pack_rules,
+    rules_by_stream_host,
+    RULE_NEGATED,
+    RULE_FAST,
     parse_line,
     KIND_RT,
     KIND_AC,
@@ -52,4 +60,5 @@ from .matcher import (  # noqa: F401
 )
 
 __all__ = ["load", "Dictionary", "HipMatcher", "FlowTable", "gen_stream", "batch_offsets", "unpack_events", "parse_line",
-           "events_by_stream_host", "BY_STREAM_UNIQUE", "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]
+           "events_by_stream_host", "BY_STREAM_UNIQUE", "pack_rules", "rules_by_stream_host",
+           "RULE_NEGATED", "RULE_FAST", "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]

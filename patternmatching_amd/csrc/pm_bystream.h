@@ -69,7 +69,21 @@ inline PmByStreamLayout pm_by_stream_layout(uint64_t cap, int64_t nseg, bool uni
     return l;
 }
 
+// The workgroups of a grid-stride launch over `items` lanes' worth of work:
+// 2,048 lanes per CU at the most, the loop beyond.
+inline int pm_bs_grid(uint64_t items, int num_cu) {
+    const uint64_t want = (items + 255) / 256;
+    const uint64_t most = (uint64_t)(num_cu > 0 ? num_cu : 256) * 8;
+    return (int)(want < 1 ? 1 : want > most ? most : want);
+}
+
 #ifdef __HIPCC__
+// The exclusive scan of cnt[0, nseg) into stream_ptr[0, nseg] (stream_ptr[nseg]
+// = the sum), three launches on s; bsum holds ceil(nseg / PM_BS_SCAN_BLOCK)
+// words.  nseg >= 1.  cnt is left as it is.
+void pm_launch_bs_scan(const unsigned long long* cnt, int64_t nseg, unsigned long long* bsum, int64_t* stream_ptr,
+                       hipStream_t s);
+
 // The passes of pm_hip_events_by_stream_device, enqueued on s in stream order
 // (nseg >= 1, cap >= 1; every pointer checked by the caller; scratch holds
 // pm_by_stream_layout(cap, nseg, unique).bytes).  Nothing is allocated and

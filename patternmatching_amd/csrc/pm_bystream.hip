@@ -18,71 +18,9 @@
 #include <hip/hip_runtime.h>
 
 #include "pm_bystream.h"
+#include "pm_bystream_dev.h"
 
 namespace {
-
-constexpr int BS_THREADS = 256;
-constexpr uint32_t BS_NO_STREAM = 0xFFFFFFFFu;
-constexpr unsigned long long BS_EMPTY = ~0ull;
-using u64 = unsigned long long;
-
-__device__ __forceinline__ uint64_t bs_used(const unsigned long long* nevents, uint64_t cap) {
-    const uint64_t c = *nevents;
-    return c < cap ? c : cap;
-}
-
-// The first index i in [lo, cnt] with offs[i] > p (cnt where none is), given
-// that every offset before lo is <= p: flow_seek's gallop, then bisection.
-// At most 2 log2(cnt) + 2 loads, every index below cnt.
-__device__ __forceinline__ int64_t bs_seek(const int64_t* __restrict__ offs, int64_t lo, int64_t cnt, int64_t p) {
-    int64_t hi = lo, step = 1;
-    while (hi < cnt && offs[hi] <= p) {
-        lo = hi + 1;
-        hi += step;
-        step <<= 1;
-    }
-    if (hi > cnt) hi = cnt;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (offs[mid] <= p) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ int64_t bs_first_lane(int64_t v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// The stream of position p: the j with offs[j] <= p < offs[j + 1]
-// (BS_NO_STREAM where none holds it, and for a lane without an event).  Called
-// by a whole wave.  A list is appended in wave-sized flushes of neighbouring
-// tiles, so the wave's events mostly lie in the leader's stream or the next
-// few: lane 0's search runs once for the wave (on scalar registers), a lane
-// inside its range [lo0, hi0) is done, a lane above it gallops on from there,
-// and only a lane below it searches from the start.  [slo, shi) = the found
-// stream's positions.
-__device__ __forceinline__ uint32_t bs_stream_of(const int64_t* __restrict__ offs, int64_t nseg, int64_t p,
-                                                 bool valid, int64_t& slo, int64_t& shi) {
-    const int64_t p0 = bs_first_lane(p);  // valid lanes are a prefix of the wave: lane 0 has an event or none has
-    int64_t j0 = bs_seek(offs, 0, nseg + 1, p0) - 1;
-    j0 = j0 < 0 ? 0 : j0 >= nseg ? nseg - 1 : j0;
-    const int64_t lo0 = offs[j0], hi0 = offs[j0 + 1];
-    slo = lo0;
-    shi = hi0;
-    if (!valid) return BS_NO_STREAM;
-    int64_t j = j0;
-    if (p < lo0 || p >= hi0) {
-        j = bs_seek(offs, p >= hi0 ? j0 + 1 : 0, nseg + 1, p) - 1;
-        j = j < 0 ? 0 : j >= nseg ? nseg - 1 : j;
-        slo = offs[j];
-        shi = offs[j + 1];
-        if (p < slo || p >= shi) return BS_NO_STREAM;  // outside every stream
-    }
-    return (uint32_t)j;
-}
 
 // Runs of equal stream indices among a wave's neighbouring lanes: a lane is a
 // head where its left neighbour's index differs (lane 0 always).  Returns the
@@ -123,8 +61,6 @@ bs_lookup_count_kernel(const uint64_t* __restrict__ events, uint64_t cap, const 
 }
 
 // ---- UNIQUE: the hash table -------------------------------------------------------
-__device__ __forceinline__ uint64_t bs_hash(uint64_t key, int shift) { return (key * 0x9E3779B97F4A7C15ull) >> shift; }
-
 // Pass 1: every used event that lies in a stream claims the slot of its key
 // stream << 24 | gid (64-bit compare-and-swap on an empty slot; linear
 // probing, at most max_probe = the table's slots steps) and folds its position
@@ -304,13 +240,15 @@ bs_scan_add_kernel(const u64* __restrict__ cnt, int64_t nseg, const u64* __restr
     if (i < nseg) stream_ptr[i] = (int64_t)(bsum[blockIdx.x] + ex);
 }
 
-int bs_grid(uint64_t items, int num_cu) {
-    const uint64_t want = (items + BS_THREADS - 1) / BS_THREADS;
-    const uint64_t most = (uint64_t)(num_cu > 0 ? num_cu : 256) * 8;  // 2,048 lanes per CU, grid-stride beyond
-    return (int)(want < 1 ? 1 : want > most ? most : want);
-}
-
 }  // namespace
+
+void pm_launch_bs_scan(const unsigned long long* cnt, int64_t nseg, unsigned long long* bsum, int64_t* stream_ptr,
+                       hipStream_t s) {
+    const int64_t nblk = (nseg + PM_BS_SCAN_BLOCK - 1) / PM_BS_SCAN_BLOCK;
+    bs_scan_sums_kernel<<<(unsigned)nblk, PM_BS_SCAN_BLOCK, 0, s>>>(cnt, nseg, bsum);
+    bs_scan_middle_kernel<<<1, PM_BS_SCAN_BLOCK, 0, s>>>(bsum, nblk, stream_ptr, nseg);
+    bs_scan_add_kernel<<<(unsigned)nblk, PM_BS_SCAN_BLOCK, 0, s>>>(cnt, nseg, bsum, stream_ptr);
+}
 
 hipError_t pm_launch_by_stream(const uint64_t* events, uint64_t cap, const unsigned long long* nevents,
                                const int64_t* offsets, int64_t nseg, bool unique, uint64_t* out, uint64_t out_cap,
@@ -323,10 +261,9 @@ hipError_t pm_launch_by_stream(const uint64_t* events, uint64_t cap, const unsig
     uint32_t* rank = (uint32_t*)(base + l.rank_off);
     u64* cnt = (u64*)(base + l.cnt_off);
     u64* bsum = (u64*)(base + l.bsum_off);
-    const int64_t nblk = (nseg + PM_BS_SCAN_BLOCK - 1) / PM_BS_SCAN_BLOCK;
     hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nseg * sizeof(u64), s);
     if (e != hipSuccess) return e;
-    const int egrid = bs_grid(cap, num_cu);
+    const int egrid = pm_bs_grid(cap, num_cu);
     if (unique) {
         // keys and pos lie back to back: one fill empties both
         e = hipMemsetAsync(keys, 0xFF, 2 * (size_t)l.table * sizeof(u64), s);
@@ -338,12 +275,10 @@ hipError_t pm_launch_by_stream(const uint64_t* events, uint64_t cap, const unsig
     } else {
         bs_lookup_count_kernel<<<egrid, BS_THREADS, 0, s>>>(events, cap, nevents, offsets, nseg, sid, cnt);
     }
-    bs_scan_sums_kernel<<<(unsigned)nblk, PM_BS_SCAN_BLOCK, 0, s>>>(cnt, nseg, bsum);
-    bs_scan_middle_kernel<<<1, PM_BS_SCAN_BLOCK, 0, s>>>(bsum, nblk, stream_ptr, nseg);
-    bs_scan_add_kernel<<<(unsigned)nblk, PM_BS_SCAN_BLOCK, 0, s>>>(cnt, nseg, bsum, stream_ptr);
+    pm_launch_bs_scan(cnt, nseg, bsum, stream_ptr, s);
     if (unique)
-        bs_table_scatter_kernel<<<bs_grid(l.table, num_cu), BS_THREADS, 0, s>>>(keys, pos, rank, l.table, nseg,
-                                                                                 stream_ptr, out, out_cap);
+        bs_table_scatter_kernel<<<pm_bs_grid(l.table, num_cu), BS_THREADS, 0, s>>>(keys, pos, rank, l.table, nseg,
+                                                                                    stream_ptr, out, out_cap);
     else
         bs_scatter_kernel<<<egrid, BS_THREADS, 0, s>>>(events, cap, nevents, sid, nseg, stream_ptr, cnt, out, out_cap);
     return hipGetLastError();

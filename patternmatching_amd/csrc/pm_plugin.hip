@@ -38,6 +38,7 @@
 #include "pm_host.h"
 #include "pm_hoststep.h"
 #include "pm_kernels.h"
+#include "pm_rules.h"
 #include "pm_streamgen.h"
 
 #ifndef PM_NT_IDS
@@ -279,6 +280,10 @@ struct BatchStage {
     size_t cap_bs_ptr = 0;
     void* d_bs_scr = nullptr;
     size_t cap_bs_scr = 0;
+    // the rules' host form (pm_hip_rules_by_stream) shares the list in, stream_ptr and the scratch above; its
+    // hits, cap_rl_hits of them
+    uint64_t* d_rl_hits = nullptr;
+    size_t cap_rl_hits = 0;
     hipStream_t s = nullptr;
 };
 // Per-pattern nocase (pm_hip_set_nocase): the images of the folded dictionary
@@ -321,7 +326,12 @@ struct PmHip {
     std::vector<uint32_t> win;  // host copy of d_win, 4 per gid (pm_hip_pattern_window)
     uint32_t* d_win = nullptr;  // in allocs
     Nocase nc;  // per-pattern nocase (pm_hip_set_nocase): nothing before its first call
-    std::string cache_dir;   // compiled-image cache (else $PM_IMAGE_CACHE)
+    // rules (pm_hip_set_rules): nothing before its first call; allocations of their own (a later call frees them)
+    PmRulesDev rules{};
+    uint32_t rules_min_len = 0;
+    std::vector<void*> rules_allocs;
+    size_t rules_bytes = 0;
+    std::string cache_dir;  // compiled-image cache (else $PM_IMAGE_CACHE)
     bool cache_hit = false;
     std::vector<void*> allocs;
     size_t table_bytes = 0;
@@ -1415,6 +1425,7 @@ void pm_hip_free(void* obj) {
     serve_free(o);  // before the tables it reads
     for (void* p : o->allocs) (void)hipFree(p);
     for (void* p : o->nc.allocs) (void)hipFree(p);
+    for (void* p : o->rules_allocs) (void)hipFree(p);
     if (o->spill) (void)hipFree(o->spill);
     for (StreamSpill& x : o->sspill) {
         if (x.buf) (void)hipFree(x.buf);
@@ -1438,6 +1449,7 @@ void pm_hip_free(void* obj) {
     if (o->batch.d_bs_out) (void)hipFree(o->batch.d_bs_out);
     if (o->batch.d_bs_ptr) (void)hipFree(o->batch.d_bs_ptr);
     if (o->batch.d_bs_scr) (void)hipFree(o->batch.d_bs_scr);
+    if (o->batch.d_rl_hits) (void)hipFree(o->batch.d_rl_hits);
     if (o->batch.s) (void)hipStreamDestroy(o->batch.s);
     free_pick(o->pick);
     for (PipeSlot& q : o->slot) {
@@ -2555,6 +2567,166 @@ int pm_hip_events_by_stream(void* obj, const uint64_t* events, size_t nevents, c
     return 0;
 }
 
+// ---- rules: which multi-pattern rules fire in each stream (pm_rules.hip) -------
+// The tables of pm_rules_image on the device, in allocations of their own: a
+// later call is a rule reload, which frees them after a device synchronize
+// (their sizes change with the rules) and uploads the new ones.
+int pm_hip_set_rules(void* obj, const uint32_t* term_ptr, const uint32_t* terms, size_t nrules) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    PmRulesImage img;
+    const size_t npat = o->gids.len.empty() ? 0 : o->gids.len.size() - 1;
+    if (o->gids.len.empty() || pm_rules_image(term_ptr, terms, nrules, o->gids.len.data(), npat, img)) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (term_ptr and terms required, 1 <= nrules <= 2^24, term_ptr from 0, 1 to 64 terms "
+                      "per rule, a positive term in each, every gid a pattern's, no gid twice in a rule, no bits but "
+                      "the gid, PM_RULE_NEGATED and PM_RULE_FAST, at most one PM_RULE_FAST per rule, none on a negated "
+                      "term)");
+        return -2;
+    }
+    PM_CHECK(hipSetDevice(o->device));
+    if (!o->rules_allocs.empty()) {
+        PM_CHECK(hipDeviceSynchronize());  // the caller has no rules call in flight; nor has this object now
+        for (void* p : o->rules_allocs) PM_CHECK(hipFree(p));
+        o->rules_allocs.clear();
+        o->table_bytes -= o->rules_bytes;
+        o->rules_bytes = 0;
+        o->rules = PmRulesDev();
+    }
+    auto up = [&](const std::vector<uint32_t>& v) {
+        void* p = nullptr;
+        const size_t bytes = v.size() * sizeof(uint32_t);
+        PM_CHECK(hipMalloc(&p, bytes));
+        PM_CHECK(hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice));
+        o->rules_allocs.push_back(p);
+        o->rules_bytes += bytes;
+        o->table_bytes += bytes;
+        return (const uint32_t*)p;
+    };
+    PmRulesDev d;
+    d.anchor_ptr = up(img.anchor_ptr);
+    d.anchor_rules = up(img.anchor_rules);
+    d.rterm_ptr = up(img.rterm_ptr);
+    d.rterms = up(img.rterms);
+    d.ngid = (uint32_t)(npat + 1);
+    d.nrules = (uint32_t)nrules;
+    d.nterms = (uint32_t)img.rterms.size();
+    o->rules = d;
+    o->rules_min_len = img.min_len;
+    return 0;
+}
+
+size_t pm_hip_rule_count(void* obj) { return as(obj)->rules.nrules; }
+
+uint32_t pm_hip_rules_min_len(void* obj) {
+    PmHip* o = as(obj);
+    return o->rules.nrules ? o->rules_min_len : 0u;
+}
+
+// Every check, then the passes; nothing is written before all of them pass.
+int pm_hip_rules_by_stream_device(void* obj, const uint64_t* d_events, uint64_t cap,
+                                  const unsigned long long* d_nevents, const int64_t* d_offsets, int64_t nseg,
+                                  uint64_t* d_hits, uint64_t hits_cap, int64_t* d_rule_ptr, void* d_scratch,
+                                  size_t scratch_bytes, void* hip_stream) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    bool ok = nseg >= 0 && nseg < PM_BS_MAX_NSEG && cap <= PM_BS_MAX_CAP && !misaligned(d_events, 8) &&
+              !misaligned(d_nevents, 8) && !misaligned(d_offsets, 8) && !misaligned(d_hits, 8) &&
+              !misaligned(d_rule_ptr, 8) && !misaligned(d_scratch, 16) && !(d_hits && d_hits == d_events) &&
+              !(cap && !d_events) && !(hits_cap && !d_hits);
+    if (ok && nseg > 0)
+        ok = d_nevents && d_offsets && d_rule_ptr && d_scratch && scratch_bytes >= pm_rules_layout(cap, nseg).bytes;
+    if (!ok) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (events, nevents, offsets, hits and rule_ptr non-NULL and 8-B aligned, scratch "
+                      "non-NULL and 16-B aligned, 0 <= nseg < 2^31, cap <= 2^40, hits != events, scratch_bytes >= "
+                      "pm_hip_rules_scratch_bytes)");
+        return -2;
+    }
+    if (!o->rules.nrules) {
+        std::snprintf(g_err, sizeof(g_err), "pm_hip_set_rules was not called: a rules call needs the rule tables");
+        return -10;
+    }
+    if (nseg == 0) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess) {
+        if (cap == 0)
+            e = hipMemsetAsync(d_rule_ptr, 0, ((size_t)nseg + 1) * sizeof(int64_t), (hipStream_t)hip_stream);
+        else
+            e = pm_launch_rules_by_stream(d_events, cap, d_nevents, d_offsets, nseg, o->rules, d_hits, hits_cap,
+                                          d_rule_ptr, d_scratch, o->num_cu, (hipStream_t)hip_stream);
+    }
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "rules launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    return 0;
+}
+
+// The host form: the list, its count and the offsets to the batch staging, the
+// device call, rule_ptr back, then the hits; where the staging's hits array
+// was too short for them it is grown to the exact count and the call repeated.
+// Each stream's range is sorted here.
+int pm_hip_rules_by_stream(void* obj, const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                           uint64_t* hits, size_t hits_cap, int64_t* rule_ptr) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    if ((nevents && !events) || (nseg && (!offsets || !rule_ptr)) || (hits_cap && !hits) ||
+        nseg >= (size_t)PM_BS_MAX_NSEG || nevents > PM_BS_MAX_CAP || (hits && hits == events)) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (events, offsets, hits and rule_ptr non-NULL, nseg < 2^31, nevents <= 2^40, hits "
+                      "!= events)");
+        return -2;
+    }
+    if (!o->rules.nrules) {
+        std::snprintf(g_err, sizeof(g_err), "pm_hip_set_rules was not called: a rules call needs the rule tables");
+        return -10;
+    }
+    if (nseg == 0) return 0;
+    if (nevents == 0) {
+        std::fill(rule_ptr, rule_ptr + nseg + 1, (int64_t)0);
+        return 0;
+    }
+    PM_CHECK(hipSetDevice(o->device));
+    BatchStage& q = o->batch;
+    batch_stage_grow(q, 0, nseg);  // the stream and the offsets
+    stage_grow((void**)&q.d_bs_in, (void**)&q.d_bs_out, sizeof(uint64_t), q.cap_bs, nevents);
+    stage_grow((void**)&q.d_bs_ptr, nullptr, sizeof(int64_t), q.cap_bs_ptr, nseg + 2);  // + the list's cursor
+    stage_grow(&q.d_bs_scr, nullptr, 1, q.cap_bs_scr, pm_rules_layout(nevents, (int64_t)nseg).bytes);
+    stage_grow((void**)&q.d_rl_hits, nullptr, sizeof(uint64_t), q.cap_rl_hits, nevents);
+    unsigned long long* d_cursor = reinterpret_cast<unsigned long long*>(q.d_bs_ptr + nseg + 1);
+    const unsigned long long cursor = nevents;
+    serve_stop(o);  // a device launch wants the whole device
+    PM_CHECK(hipMemcpyAsync(q.d_bs_in, events, nevents * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(d_cursor, &cursor, sizeof(cursor), hipMemcpyHostToDevice, q.s));
+    std::vector<int64_t> ptr(nseg + 1);
+    for (int turn = 0; turn < 2; ++turn) {
+        const hipError_t e = pm_launch_rules_by_stream(q.d_bs_in, nevents, d_cursor, q.d_offs, (int64_t)nseg, o->rules,
+                                                       q.d_rl_hits, q.cap_rl_hits, q.d_bs_ptr, q.d_bs_scr, o->num_cu, q.s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(q.s);
+            std::snprintf(g_err, sizeof(g_err), "rules launch: %s", hipGetErrorString(e));
+            return -3;
+        }
+        PM_CHECK(hipMemcpyAsync(ptr.data(), q.d_bs_ptr, ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, q.s));
+        PM_CHECK(hipStreamSynchronize(q.s));
+        if ((size_t)ptr[nseg] <= q.cap_rl_hits) break;  // (the second turn's array holds the first's exact count)
+        stage_grow((void**)&q.d_rl_hits, nullptr, sizeof(uint64_t), q.cap_rl_hits, (size_t)ptr[nseg]);
+    }
+    const size_t total = (size_t)ptr[nseg];
+    std::vector<uint64_t> hv(total);
+    if (total) PM_CHECK(hipMemcpyAsync(hv.data(), q.d_rl_hits, total * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    PM_CHECK(hipStreamSynchronize(q.s));
+    par_range(nseg, (size_t)1 << 12, [&](size_t lo, size_t hi) {
+        for (size_t j = lo; j < hi; ++j) std::sort(hv.begin() + ptr[j], hv.begin() + ptr[j + 1]);
+    });
+    std::memcpy(rule_ptr, ptr.data(), ptr.size() * sizeof(int64_t));
+    if (hits_cap && total) std::memcpy(hits, hv.data(), std::min(hits_cap, total) * sizeof(uint64_t));
+    return 0;
+}
+
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,
                         unsigned long long* d_counts, void* hip_stream) {
     PmHip* o = as(obj);
@@ -2617,6 +2789,7 @@ size_t pm_hip_scratch_bytes(void* obj) {
     if (o->batch.d_bs_in) b += 2 * o->batch.cap_bs * sizeof(uint64_t);
     if (o->batch.d_bs_ptr) b += o->batch.cap_bs_ptr * sizeof(int64_t);
     if (o->batch.d_bs_scr) b += o->batch.cap_bs_scr;
+    if (o->batch.d_rl_hits) b += o->batch.cap_rl_hits * sizeof(uint64_t);
     return b;
 }
 

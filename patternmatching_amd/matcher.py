@@ -184,6 +184,60 @@ def events_by_stream_host(events, offsets, unique=True, out_cap=None):
     return ptr, out[:min(len(out), int(ptr[-1]))]
 
 
+RULE_NEGATED = 1 << 31  # PM_RULE_NEGATED: the term must NOT be in the stream's set
+RULE_FAST = 1 << 30     # PM_RULE_FAST: the term is the rule's anchor (the caller's fast_pattern)
+
+
+def pack_rules(rules, fast=None):
+    """(term_ptr u32 of len(rules) + 1, terms u32): the CSR form that
+    pm_hip_set_rules takes.  A rule is a sequence of ints: g is a positive
+    term (pattern gid g), -g a negated one; fast[r] is the gid of rule r's
+    RULE_FAST term, or None."""
+    rules = [list(r) for r in rules]
+    if fast is not None and len(fast) != len(rules):
+        raise ValueError("fast: one gid or None per rule")
+    ptr = np.zeros(len(rules) + 1, dtype=np.uint32)
+    terms = []
+    for r, rule in enumerate(rules):
+        f = None if fast is None else fast[r]
+        if f is not None and f not in rule:
+            raise ValueError(f"fast[{r}] = {f} is no positive term of rule {r}")
+        for g in rule:
+            g = int(g)
+            if g == 0 or abs(g) >= 1 << EVENT_GID_BITS:
+                raise ValueError(f"rule {r}: a term is a gid in [1, 2^24) or its negative, not {g}")
+            terms.append((-g | RULE_NEGATED) if g < 0 else (g | RULE_FAST) if g == f else g)
+        ptr[r + 1] = len(terms)
+    return ptr, np.asarray(terms, dtype=np.uint32)
+
+
+def rules_by_stream_host(events, offsets, rules, hits_cap=None):
+    """pm_flat_rules_by_stream, the host twin of HipMatcher.rules_by_stream (no
+    matcher, no device): (rule_ptr int64 of nseg + 1, hits u64 of position <<
+    24 | rule) with each stream's range ascending; rules as pack_rules takes
+    them, or its (term_ptr, terms) pair.  The twin sees only the list: it is
+    exact for a list from an all-matches scan at a min_len no larger than the
+    shortest term with a cap that held every event."""
+    ev = np.ascontiguousarray(events, dtype=np.uint64).ravel()
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offs.ndim != 1 or offs.size < 1:
+        raise ValueError("offsets: nseg + 1 values")
+    tptr, terms = rules if isinstance(rules, tuple) else pack_rules(rules)
+    u64p, i64p, u32p = (ctypes.POINTER(t) for t in (ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32))
+    ptr = np.zeros(offs.size, dtype=np.int64)
+    hits = np.empty(0 if hits_cap is None else hits_cap, dtype=np.uint64)
+    for _ in range(2):  # the hits are not bounded by the events: the first call counts them
+        rc = load().pm_flat_rules_by_stream(ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p), offs.size - 1,
+                                            tptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p), len(tptr) - 1,
+                                            hits.ctypes.data_as(u64p), len(hits), ptr.ctypes.data_as(i64p))
+        if rc != 0:
+            raise ValueError(f"pm_flat_rules_by_stream: bad arguments ({rc})")
+        if hits_cap is not None or len(hits) >= ptr[-1]:
+            break
+        hits = np.empty(int(ptr[-1]), dtype=np.uint64)
+    return ptr, hits[:min(len(hits), int(ptr[-1]))]
+
+
 class FlowTable:
     """The carried states of many live flows over one matcher (ac / auto
     kinds): a dict of flow key -> flow state, and one flow call
@@ -701,6 +755,83 @@ class HipMatcher:
         pos, gids = unpack_events(ev)
         codes = self._codes[gids]
         return [(pos[ptr[j]:ptr[j + 1]] - offs[j], codes[ptr[j]:ptr[j + 1]]) for j in range(len(buffers))]
+
+    # --- rules: which multi-pattern rules fire in each stream ------------------
+    def set_rules(self, rules, fast=None):
+        """pm_hip_set_rules: a rule is a sequence of 1 to 64 ints, g a
+        positive term (pattern gid g must be in the stream's set), -g a
+        negated one (it must not); fast[r] is the gid of rule r's anchor (its
+        fast_pattern) or None (the longest positive term).  After compile(); a
+        later call replaces the rules (no rules call may be in flight)."""
+        ptr, terms = pack_rules(rules, fast)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self.lib.pm_hip_set_rules(self.obj, ptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
+                                              len(ptr) - 1))
+
+    def rule_count(self):
+        """pm_hip_rule_count: the rules set (0 before set_rules)."""
+        return int(self.lib.pm_hip_rule_count(self.obj))
+
+    def rules_min_len(self):
+        """pm_hip_rules_min_len: the length of the shortest pattern any term
+        names: the largest min_len a scan may use for exact rule hits (0
+        before set_rules)."""
+        return int(self.lib.pm_hip_rules_min_len(self.obj))
+
+    def rules_scratch_bytes(self, cap, nseg):
+        """pm_hip_rules_scratch_bytes: the device scratch, in bytes, that
+        rules_by_stream_device needs for a list of cap slots over nseg streams."""
+        b = self.lib.pm_hip_rules_scratch_bytes(cap, nseg)
+        if b == ctypes.c_size_t(-1).value:
+            raise ValueError("rules_scratch_bytes: cap <= 2^40, 0 <= nseg < 2^31")
+        return b
+
+    def rules_by_stream_device(self, d_events_ptr, cap, d_nevents_ptr, d_offsets_ptr, nseg, d_hits_ptr, hits_cap,
+                               d_rule_ptr_ptr, d_scratch_ptr, scratch_bytes, stream_ptr):
+        """pm_hip_rules_by_stream_device: the rules that fire in each of the
+        scan's streams, from the list the scan left in d_events_ptr[0, cap)
+        behind the device cursor d_nevents_ptr: stream j's hits (position <<
+        24 | rule) to d_hits_ptr[ptr[j] .. ptr[j+1]) with ptr = the nseg + 1
+        int64 at d_rule_ptr_ptr, exact whatever hits_cap is.  Enqueued on
+        stream_ptr, no synchronize.  Rules see only what the list holds: scan
+        with an all-matches form, at a min_len <= rules_min_len(), with a cap
+        that holds the whole list."""
+        rc = self.lib.pm_hip_rules_by_stream_device(self.obj, d_events_ptr, cap, d_nevents_ptr, d_offsets_ptr, nseg,
+                                                    d_hits_ptr, hits_cap, d_rule_ptr_ptr, d_scratch_ptr, scratch_bytes,
+                                                    stream_ptr)
+        self._check(rc)
+
+    def rules_by_stream(self, events, offsets):
+        """pm_hip_rules_by_stream: host arrays through the device call:
+        (rule_ptr int64 of nseg + 1, hits u64), stream j's hits
+        hits[ptr[j]:ptr[j+1]] ascending, each position << 24 | rule with the
+        position at which the rule's last positive term first appeared
+        (unpack_events splits them).  Rules see only what the list holds:
+        events from an all-matches scan, at a min_len <= rules_min_len(), with
+        a cap that held the whole list."""
+        ev, offs, _, ptr = _by_stream_host_args(events, offsets, 0)
+        u64p, i64p = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64)
+        hits = np.empty(max(len(ev), 1), dtype=np.uint64)
+        for _ in range(2):  # the hits are not bounded by the events: rule_ptr[-1] sizes the retry
+            rc = self.lib.pm_hip_rules_by_stream(self.obj, ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p),
+                                                 offs.size - 1, hits.ctypes.data_as(u64p), len(hits),
+                                                 ptr.ctypes.data_as(i64p))
+            self._check(rc)
+            if len(hits) >= ptr[-1]:
+                break
+            hits = np.empty(int(ptr[-1]), dtype=np.uint64)
+        return ptr, hits[:int(ptr[-1])]
+
+    def read_many_rules(self, buffers):
+        """One all-matches batch list call over a list of bytes-like streams at
+        rules_min_len(), then rules_by_stream: per stream, in order,
+        (positions inside the stream, rule indices) of the rules that fire in
+        it, ascending by position."""
+        data, offs = _concat(buffers)
+        ev, _ = self._read_events(data, offs, None, self.rules_min_len(), all_matches=True)
+        ptr, hits = self.rules_by_stream(ev, offs)
+        pos, rule = unpack_events(hits)
+        return [(pos[ptr[j]:ptr[j + 1]] - offs[j], rule[ptr[j]:ptr[j + 1]]) for j in range(len(buffers))]
 
     # --- pattern groups: a group mask per pattern and one per stream --------
     def set_groups(self, masks):
