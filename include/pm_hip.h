@@ -667,8 +667,9 @@ int pm_flat_events_by_stream(const uint64_t* events, size_t nevents, const int64
  *     a scan leaves out every pattern shorter than its min_len;
  *   - with a cap that holds the whole list: an overflowed list lacks events,
  *     so positive terms may miss and negated ones pass.
- * Flows are out of scope: a rule is evaluated over the streams of one call,
- * and no set is carried from one packet of a flow to the next.
+ * This call knows no flows: a rule is evaluated over the streams of one call,
+ * and no set is carried from one packet of a flow to the next.  The flow rules
+ * below (pm_hip_flow_rules_device) carry a set per flow.
  * pm_hip_set_rules: the rules in CSR form.  term_ptr has nrules + 1 values,
  * starts at 0 and does not decrease; rule r's terms are terms[term_ptr[r] ..
  * term_ptr[r+1]).  A term holds the gid in bits 0-23; PM_RULE_NEGATED (bit
@@ -766,6 +767,147 @@ int pm_flat_rule_tables(const uint32_t* term_ptr, const uint32_t* terms, size_t 
 int pm_flat_rules_by_stream(const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
                             const uint32_t* term_ptr, const uint32_t* terms, size_t nrules, uint64_t* hits,
                             size_t hits_cap, int64_t* rule_ptr);
+
+/*
+ * Flow rules: rules whose terms lie in different packets of one flow.  The
+ * flow scans (pm_hip_scan_flows_*_device) are exact across packet cuts: they
+ * report a pattern that begins in one call and ends in the next.  The flow
+ * rules are the rules behind them: the caller keeps one set of term bits per
+ * live flow ON THE DEVICE, and one call, behind any list scan, reports the
+ * rules whose conjunction became true in this call's bytes and folds this
+ * call's patterns into the flows' sets.
+ * Rule set.  pm_hip_set_flow_rules takes a rule set of its own, in the CSR
+ * form, with the term format and every check of pm_hip_set_rules (1 to 64
+ * terms, PM_RULE_NEGATED, PM_RULE_FAST; -1 before compile(); -2, with one
+ * message naming every constraint, for the same cases; nothing changes on an
+ * error).  It is independent of pm_hip_set_rules, which it does not touch: an
+ * object may hold both sets, neither, or either one.  Its device tables (the
+ * bit of each gid; an inverted index from EVERY positive term's gid to the
+ * rules that carry it; each rule's full term list, the PM_RULE_FAST term --
+ * else the longest positive pattern, ties to the smaller gid -- first, then
+ * the other positive terms, then the negated ones) live in allocations of
+ * their own, counted in pm_hip_table_bytes, replaced by a later call after a
+ * device synchronize (no flow-rules call may be in flight) and freed with the
+ * object; compile() and the compiled-image cache do not see them.
+ * PM_RULE_FAST cannot gate verification here, because the anchor may be a
+ * carried term: it is accepted and only decides which term is tested first.
+ * pm_hip_flow_rule_count: the rules set (0 before).
+ * pm_hip_flow_rules_min_len: the length of the shortest pattern any term
+ * names (0 before).
+ * Bits.  K is the number of distinct gids named by any term, positive or
+ * negated.  The bit of a gid is its rank among those gids, ascending.  A
+ * flow's set has W = max(1, ceil(K / 64)) u64 words (pm_hip_flow_rule_words;
+ * 0 before); bit b lives in word b >> 6 at bit b & 63.  Bits at or above K
+ * are ignored when read and never set.  The numbering is public --
+ * pm_hip_flow_rule_bit(obj, gid): the bit, or -1 for a gid that no term names
+ * and before pm_hip_set_flow_rules; pm_flat_flow_rule_bits on the host alone
+ * -- so the host twin's sets and the device's are bit-identical.
+ * State.  d_sets is a device array of nrows x W u64, owned by the caller, a
+ * row per live flow.  d_rows[j] (int64, nseg of them) names the row of the
+ * call's stream j; NULL means stream j uses row j, which needs nrows >= nseg.
+ * A zeroed row is a fresh flow, and the caller ends a flow by zeroing its
+ * row.  A row index outside [0, nrows) makes its stream inert: no hits,
+ * nothing written.  One row named by two streams of one call gives
+ * unspecified sets and hits for those streams, never an access outside the
+ * arrays.
+ * Semantics: the rules semantics above, applied to the flow's prefix.  Let C
+ * be the gids whose bit is set in the flow's row before the call (the carried
+ * terms), and N the term gids with at least one used event inside the stream
+ * in this call that are not in C, each with its first (smallest) position in
+ * this call.  Rule r gives a hit in this call iff every positive term is in
+ * C u N, at least one positive term is in N, and no negated term is in C u N.
+ * The hit is position << 24 | r with the largest first position among the
+ * positive terms in N: buffer-global, the events' own format (carried terms
+ * became true in earlier calls and cannot be the largest).  This equals the
+ * hits of pm_hip_rules_by_stream_device over everything the flow has had
+ * through this call, scanned as one stream, restricted to the hits whose
+ * position lies in this call's bytes.  So:
+ *   - a rule fires at most once per flow;
+ *   - a negated term seen in an earlier call, or anywhere in this call (even
+ *     after the completing byte), suppresses the rule;
+ *   - a negated term that first appears in a later call does not retract a
+ *     hit already reported.
+ * Commit.  After the hits are written, every gid of N has its bit OR-ed into
+ * its flow's row.  With PM_FLOW_RULES_KEEP in flags the rows are left
+ * untouched: a count-only or dry call, used to size hits_cap.  Without it
+ * the rows are updated whatever hits_cap is, and d_rule_ptr is exact either
+ * way, as in the rules call.  After a commit the same call reports nothing
+ * (every term is carried), so a caller who cannot bound the hits sizes them
+ * with a PM_FLOW_RULES_KEEP call first and then commits once.
+ * The list has the rules call's preconditions: an all-matches form, at a
+ * min_len <= pm_hip_flow_rules_min_len, with a cap that held the list; and it
+ * must come from a flow scan that continued the same flows, which is what
+ * makes a pattern that straddles a cut appear.  Otherwise the call does not
+ * care which scan made the list: plain, group, window and nocase lists work.
+ * pm_hip_flow_rules_device: d_events, cap, d_nevents, d_offsets, nseg,
+ * d_hits, hits_cap, d_rule_ptr, d_scratch, scratch_bytes and hip_stream are
+ * exactly those of pm_hip_rules_by_stream_device, with its guarantees: the
+ * cursor is read on the device; the call allocates nothing, does not
+ * synchronize on the host and may be captured; it asks the resident
+ * read_block server to leave the device first; hits inside a range come in
+ * unspecified order and nothing at or past d_hits[hits_cap] is written.
+ * Scratch: pm_hip_flow_rules_scratch_bytes(cap, nseg) bytes exactly, the
+ * rules call's formula:
+ *     16 T + r16(8 nseg) + r16(8 ceil(nseg / 1024))
+ * T = the power of two >= max(2 cap, 64), r16 rounding up to 16; (size_t)-1
+ * for arguments the call would reject.
+ * Returns 0; -1 before compile(); -2 bad arguments, one message for all of
+ * the rules call's cases and: d_sets NULL with nrows > 0, d_sets or d_rows
+ * misaligned (8 bytes), nrows < 0 or nrows x W above 2^40 words, d_rows NULL
+ * with nrows < nseg, a flag bit other than PM_FLOW_RULES_KEEP; -11
+ * pm_hip_set_flow_rules was not called (whether or not pm_hip_set_rules was);
+ * -3 launch error.  Nothing is launched or written when a check fails.
+ * nseg == 0: returns 0 and launches nothing.  cap == 0 with nseg > 0: an
+ * all-zero d_rule_ptr and untouched sets.
+ * Memory safety does not depend on the data: beyond the rules call's clamps a
+ * row index is tested against nrows wherever it is read, a bit against 64 W
+ * and an index range against the index array; garbage offsets, events, rows
+ * or sets give unspecified hits and sets, never an access outside the arrays
+ * named here.
+ * pm_hip_flow_rules: the host form.  events, offsets, sets (nrows x W,
+ * updated in place), rows (nseg of them, or NULL) and the outputs are HOST
+ * arrays; it stages them on the object's batch stream (staging counted in
+ * pm_hip_scratch_bytes) and runs the device call so that the committing call
+ * runs exactly once: where its hits staging may be too short it counts the
+ * hits with a PM_FLOW_RULES_KEEP call first.  It sorts each stream's range
+ * ascending, hands over rule_ptr and the first min(hits_cap, total) hits and
+ * copies the sets back.  -1, -2, -11 and -3 as above where they apply.
+ * pm_flat_flow_rule_bits, pm_flat_flow_rules: the host alone, no handle and
+ * no device; they set no message.  pm_flat_flow_rule_bits runs the checks of
+ * pm_hip_set_flow_rules that need no pattern lengths (a gid must lie in [1,
+ * npat]) and gives bit_by_gid_out[npat + 1] (0xFFFFFFFF: no term) and
+ * *nbits_out = K; 0, or -2 with nothing written.  pm_flat_flow_rules is the
+ * twin of the device call over host arrays, the sets updated in place, each
+ * range sorted ascending; words must be the rule set's W; 0, or -2 for what
+ * the device call rejects (and a wrong words), with nothing written.
+ * Measured (snort, 64 MiB in 44,740 packets of 1,500 bytes, one per flow and
+ * call, two calls behind the flow scan at min_len 3, 10,000 synthetic rules
+ * over 20,981 term gids, W = 328; profiles/flowrules/): the call alone takes
+ * 0.12 ms on random ASCII (51 thousand events), 0.32x the scan, and 8.9-10.2
+ * ms on the lines stream (14.6 million events), 3.7-4.4x the scan; against
+ * the UNIQUE sets copied to the host and walked by pm_flat_flow_rules on one
+ * thread 0.0060-0.0079x ("Flow rules").
+ */
+#define PM_FLOW_RULES_KEEP 1u
+int pm_hip_set_flow_rules(void* obj, const uint32_t* term_ptr, const uint32_t* terms, size_t nrules);
+size_t pm_hip_flow_rule_count(void* obj);
+uint32_t pm_hip_flow_rules_min_len(void* obj);
+uint32_t pm_hip_flow_rule_words(void* obj);
+int64_t pm_hip_flow_rule_bit(void* obj, uint32_t gid);
+size_t pm_hip_flow_rules_scratch_bytes(uint64_t cap, int64_t nseg);
+int pm_hip_flow_rules_device(void* obj, const uint64_t* d_events, uint64_t cap, const unsigned long long* d_nevents,
+                             const int64_t* d_offsets, int64_t nseg, uint64_t* d_sets, int64_t nrows,
+                             const int64_t* d_rows, uint32_t flags, uint64_t* d_hits, uint64_t hits_cap,
+                             int64_t* d_rule_ptr, void* d_scratch, size_t scratch_bytes, void* hip_stream);
+int pm_hip_flow_rules(void* obj, const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                      uint64_t* sets, size_t nrows, const int64_t* rows, uint32_t flags, uint64_t* hits,
+                      size_t hits_cap, int64_t* rule_ptr);
+int pm_flat_flow_rule_bits(const uint32_t* term_ptr, const uint32_t* terms, size_t nrules, size_t npat,
+                           uint32_t* bit_by_gid_out, uint32_t* nbits_out);
+int pm_flat_flow_rules(const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                       const uint32_t* term_ptr, const uint32_t* terms, size_t nrules, uint64_t* sets, size_t nrows,
+                       size_t words, const int64_t* rows, uint32_t flags, uint64_t* hits, size_t hits_cap,
+                       int64_t* rule_ptr);
 
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,

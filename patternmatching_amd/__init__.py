@@ -38,6 +38,12 @@ interface:
                     terms, pack_rules) fire in each stream of such a list,
                     without a device (the host twin of HipMatcher.set_rules /
                     rules_by_stream / rules_by_stream_device / read_many_rules)
+    flow_rules_host         the rules whose terms lie in different packets of a
+                    flow: a set of carried terms per flow, the rules that
+                    become true in each call, without a device (the host twin
+                    of HipMatcher.set_flow_rules / flow_rules /
+                    flow_rules_device and FlowTable.scan_rules;
+                    flow_rule_bits_host gives the sets' bit numbering)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401
@@ -51,6 +57,9 @@ from .matcher import (  # noqa: F401
     BY_STREAM_UNIQUE,
     pack_rules,
     rules_by_stream_host,
+    flow_rules_host,
+    flow_rule_bits_host,
+    FLOW_RULES_KEEP,
     RULE_NEGATED,
     RULE_FAST,
     parse_line,
@@ -61,4 +70,4 @@ from .matcher import (  # noqa: F401
 
 __all__ = ["load", "Dictionary", "HipMatcher", "FlowTable", "gen_stream", "batch_offsets", "unpack_events", "parse_line",
            "events_by_stream_host", "BY_STREAM_UNIQUE", "pack_rules", "rules_by_stream_host",
-           "RULE_NEGATED", "RULE_FAST", "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]
+           "flow_rules_host", "flow_rule_bits_host", "FLOW_RULES_KEEP", "RULE_NEGATED", "RULE_FAST", "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]

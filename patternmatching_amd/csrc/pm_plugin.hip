@@ -38,6 +38,7 @@
 #include "pm_host.h"
 #include "pm_hoststep.h"
 #include "pm_kernels.h"
+#include "pm_flowrules.h"
 #include "pm_rules.h"
 #include "pm_streamgen.h"
 
@@ -284,6 +285,12 @@ struct BatchStage {
     // hits, cap_rl_hits of them
     uint64_t* d_rl_hits = nullptr;
     size_t cap_rl_hits = 0;
+    // the flow rules' host form (pm_hip_flow_rules) shares all of the rules' staging; its sets, cap_fr_sets
+    // words, and its rows, cap_fr_rows of them
+    uint64_t* d_fr_sets = nullptr;
+    size_t cap_fr_sets = 0;
+    int64_t* d_fr_rows = nullptr;
+    size_t cap_fr_rows = 0;
     hipStream_t s = nullptr;
 };
 // Per-pattern nocase (pm_hip_set_nocase): the images of the folded dictionary
@@ -331,6 +338,13 @@ struct PmHip {
     uint32_t rules_min_len = 0;
     std::vector<void*> rules_allocs;
     size_t rules_bytes = 0;
+    // flow rules (pm_hip_set_flow_rules): a rule set of their own, held the same way
+    PmFlowRulesDev flow_rules{};
+    uint32_t flow_rules_min_len = 0;
+    uint32_t flow_rules_fanout = 0;  // the most rules one gid indexes (bounds the host form's hits)
+    std::vector<uint32_t> flow_rule_bits;  // host copy of gid_bit (pm_hip_flow_rule_bit)
+    std::vector<void*> flow_rules_allocs;
+    size_t flow_rules_bytes = 0;
     std::string cache_dir;  // compiled-image cache (else $PM_IMAGE_CACHE)
     bool cache_hit = false;
     std::vector<void*> allocs;
@@ -1426,6 +1440,7 @@ void pm_hip_free(void* obj) {
     for (void* p : o->allocs) (void)hipFree(p);
     for (void* p : o->nc.allocs) (void)hipFree(p);
     for (void* p : o->rules_allocs) (void)hipFree(p);
+    for (void* p : o->flow_rules_allocs) (void)hipFree(p);
     if (o->spill) (void)hipFree(o->spill);
     for (StreamSpill& x : o->sspill) {
         if (x.buf) (void)hipFree(x.buf);
@@ -1450,6 +1465,8 @@ void pm_hip_free(void* obj) {
     if (o->batch.d_bs_ptr) (void)hipFree(o->batch.d_bs_ptr);
     if (o->batch.d_bs_scr) (void)hipFree(o->batch.d_bs_scr);
     if (o->batch.d_rl_hits) (void)hipFree(o->batch.d_rl_hits);
+    if (o->batch.d_fr_sets) (void)hipFree(o->batch.d_fr_sets);
+    if (o->batch.d_fr_rows) (void)hipFree(o->batch.d_fr_rows);
     if (o->batch.s) (void)hipStreamDestroy(o->batch.s);
     free_pick(o->pick);
     for (PipeSlot& q : o->slot) {
@@ -2727,6 +2744,206 @@ int pm_hip_rules_by_stream(void* obj, const uint64_t* events, size_t nevents, co
     return 0;
 }
 
+// ---- flow rules: rules over a set per flow carried on the device (pm_flowrules.hip) ----
+// The tables of pm_flow_rules_image on the device, in allocations of their
+// own, replaced like the rules' tables.  pm_hip_set_rules and its tables are
+// not touched.
+int pm_hip_set_flow_rules(void* obj, const uint32_t* term_ptr, const uint32_t* terms, size_t nrules) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    PmFlowRulesImage img;
+    const size_t npat = o->gids.len.empty() ? 0 : o->gids.len.size() - 1;
+    if (o->gids.len.empty() || pm_flow_rules_image(term_ptr, terms, nrules, o->gids.len.data(), npat, img)) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (term_ptr and terms required, 1 <= nrules <= 2^24, term_ptr from 0, 1 to 64 terms "
+                      "per rule, a positive term in each, every gid a pattern's, no gid twice in a rule, no bits but "
+                      "the gid, PM_RULE_NEGATED and PM_RULE_FAST, at most one PM_RULE_FAST per rule, none on a negated "
+                      "term)");
+        return -2;
+    }
+    PM_CHECK(hipSetDevice(o->device));
+    if (!o->flow_rules_allocs.empty()) {
+        PM_CHECK(hipDeviceSynchronize());  // the caller has no flow-rules call in flight; nor has this object now
+        for (void* p : o->flow_rules_allocs) PM_CHECK(hipFree(p));
+        o->flow_rules_allocs.clear();
+        o->table_bytes -= o->flow_rules_bytes;
+        o->flow_rules_bytes = 0;
+        o->flow_rules = PmFlowRulesDev();
+    }
+    auto up = [&](const std::vector<uint32_t>& v) {
+        void* p = nullptr;
+        const size_t bytes = v.size() * sizeof(uint32_t);
+        PM_CHECK(hipMalloc(&p, bytes));
+        PM_CHECK(hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice));
+        o->flow_rules_allocs.push_back(p);
+        o->flow_rules_bytes += bytes;
+        o->table_bytes += bytes;
+        return (const uint32_t*)p;
+    };
+    PmFlowRulesDev d;
+    d.gid_bit = up(img.gid_bit);
+    d.idx_ptr = up(img.idx_ptr);
+    d.idx_rules = up(img.idx_rules);
+    d.rterm_ptr = up(img.rterm_ptr);
+    d.rterms = up(img.rterms);
+    d.ngid = (uint32_t)(npat + 1);
+    d.nrules = (uint32_t)nrules;
+    d.nidx = (uint32_t)img.idx_rules.size();
+    d.nterms = (uint32_t)img.rterms.size();
+    d.words = img.words;
+    o->flow_rules = d;
+    o->flow_rules_min_len = img.min_len;
+    o->flow_rules_fanout = img.max_fanout;
+    o->flow_rule_bits = std::move(img.gid_bit);
+    return 0;
+}
+
+size_t pm_hip_flow_rule_count(void* obj) { return as(obj)->flow_rules.nrules; }
+
+uint32_t pm_hip_flow_rules_min_len(void* obj) {
+    PmHip* o = as(obj);
+    return o->flow_rules.nrules ? o->flow_rules_min_len : 0u;
+}
+
+uint32_t pm_hip_flow_rule_words(void* obj) { return as(obj)->flow_rules.words; }
+
+int64_t pm_hip_flow_rule_bit(void* obj, uint32_t gid) {
+    PmHip* o = as(obj);
+    if (!o->flow_rules.nrules || gid >= o->flow_rule_bits.size() || o->flow_rule_bits[gid] == PM_FR_NO_BIT) return -1;
+    return (int64_t)o->flow_rule_bits[gid];
+}
+
+// Every check, then the passes; nothing is written before all of them pass.
+int pm_hip_flow_rules_device(void* obj, const uint64_t* d_events, uint64_t cap, const unsigned long long* d_nevents,
+                             const int64_t* d_offsets, int64_t nseg, uint64_t* d_sets, int64_t nrows,
+                             const int64_t* d_rows, uint32_t flags, uint64_t* d_hits, uint64_t hits_cap,
+                             int64_t* d_rule_ptr, void* d_scratch, size_t scratch_bytes, void* hip_stream) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    const uint64_t W = o->flow_rules.words ? o->flow_rules.words : 1;  // (before pm_hip_set_flow_rules: -11 below)
+    bool ok = nseg >= 0 && nseg < PM_BS_MAX_NSEG && cap <= PM_BS_MAX_CAP && !misaligned(d_events, 8) &&
+              !misaligned(d_nevents, 8) && !misaligned(d_offsets, 8) && !misaligned(d_hits, 8) &&
+              !misaligned(d_rule_ptr, 8) && !misaligned(d_scratch, 16) && !misaligned(d_sets, 8) &&
+              !misaligned(d_rows, 8) && !(d_hits && d_hits == d_events) && !(cap && !d_events) &&
+              !(hits_cap && !d_hits) && !(flags & ~PM_FR_KEEP) && nrows >= 0 &&
+              (uint64_t)nrows <= PM_FR_MAX_WORDS / W && !(nrows > 0 && !d_sets) && !(!d_rows && nrows < nseg);
+    if (ok && nseg > 0)
+        ok = d_nevents && d_offsets && d_rule_ptr && d_scratch && scratch_bytes >= pm_rules_layout(cap, nseg).bytes;
+    if (!ok) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (events, nevents, offsets, sets, rows, hits and rule_ptr 8-B aligned and, but for "
+                      "rows, non-NULL, scratch non-NULL and 16-B aligned, 0 <= nseg < 2^31, cap <= 2^40, 0 <= nrows, "
+                      "nrows x words <= 2^40, nrows >= nseg without rows, no flag but PM_FLOW_RULES_KEEP, hits != "
+                      "events, scratch_bytes >= pm_hip_flow_rules_scratch_bytes)");
+        return -2;
+    }
+    if (!o->flow_rules.nrules) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "pm_hip_set_flow_rules was not called: a flow-rules call needs the rule tables");
+        return -11;
+    }
+    if (nseg == 0) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess) {
+        if (cap == 0)
+            e = hipMemsetAsync(d_rule_ptr, 0, ((size_t)nseg + 1) * sizeof(int64_t), (hipStream_t)hip_stream);
+        else
+            e = pm_launch_flow_rules(d_events, cap, d_nevents, d_offsets, nseg, o->flow_rules, d_sets, nrows, d_rows,
+                                     (flags & PM_FR_KEEP) != 0, d_hits, hits_cap, d_rule_ptr, d_scratch, o->num_cu,
+                                     (hipStream_t)hip_stream);
+    }
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "flow rules launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    return 0;
+}
+
+// The host form: the list, its count, the offsets, the rows and the sets to
+// the batch staging, the device call, rule_ptr back, then the hits and the
+// sets.  The committing call runs exactly once: where the staging's hits array
+// may be too short (it holds fewer than the bound min(streams x rules, events
+// x the most rules a gid indexes)), a PM_FLOW_RULES_KEEP call counts them
+// first and the array is grown to the exact count.  Each stream's range is
+// sorted here.
+int pm_hip_flow_rules(void* obj, const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                      uint64_t* sets, size_t nrows, const int64_t* rows, uint32_t flags, uint64_t* hits,
+                      size_t hits_cap, int64_t* rule_ptr) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    const uint64_t W = o->flow_rules.words ? o->flow_rules.words : 1;
+    if ((nevents && !events) || (nseg && (!offsets || !rule_ptr)) || (hits_cap && !hits) ||
+        nseg >= (size_t)PM_BS_MAX_NSEG || nevents > PM_BS_MAX_CAP || (hits && hits == events) ||
+        (flags & ~PM_FR_KEEP) || (nrows && !sets) || nrows > PM_FR_MAX_WORDS / W || (!rows && nrows < nseg)) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (events, offsets, sets, hits and rule_ptr non-NULL, nseg < 2^31, nevents <= 2^40, "
+                      "nrows x words <= 2^40, nrows >= nseg without rows, no flag but PM_FLOW_RULES_KEEP, hits != "
+                      "events)");
+        return -2;
+    }
+    if (!o->flow_rules.nrules) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "pm_hip_set_flow_rules was not called: a flow-rules call needs the rule tables");
+        return -11;
+    }
+    if (nseg == 0) return 0;
+    if (nevents == 0) {
+        std::fill(rule_ptr, rule_ptr + nseg + 1, (int64_t)0);
+        return 0;
+    }
+    PM_CHECK(hipSetDevice(o->device));
+    BatchStage& q = o->batch;
+    const size_t nwords = nrows * (size_t)W;
+    batch_stage_grow(q, 0, nseg);  // the stream and the offsets
+    stage_grow((void**)&q.d_bs_in, (void**)&q.d_bs_out, sizeof(uint64_t), q.cap_bs, nevents);
+    stage_grow((void**)&q.d_bs_ptr, nullptr, sizeof(int64_t), q.cap_bs_ptr, nseg + 2);  // + the list's cursor
+    stage_grow(&q.d_bs_scr, nullptr, 1, q.cap_bs_scr, pm_rules_layout(nevents, (int64_t)nseg).bytes);
+    stage_grow((void**)&q.d_rl_hits, nullptr, sizeof(uint64_t), q.cap_rl_hits, nevents);
+    stage_grow((void**)&q.d_fr_sets, nullptr, sizeof(uint64_t), q.cap_fr_sets, std::max(nwords, (size_t)1));
+    if (rows) stage_grow((void**)&q.d_fr_rows, nullptr, sizeof(int64_t), q.cap_fr_rows, nseg);
+    unsigned long long* d_cursor = reinterpret_cast<unsigned long long*>(q.d_bs_ptr + nseg + 1);
+    const unsigned long long cursor = nevents;
+    serve_stop(o);  // a device launch wants the whole device
+    PM_CHECK(hipMemcpyAsync(q.d_bs_in, events, nevents * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(d_cursor, &cursor, sizeof(cursor), hipMemcpyHostToDevice, q.s));
+    if (nwords) PM_CHECK(hipMemcpyAsync(q.d_fr_sets, sets, nwords * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    if (rows) PM_CHECK(hipMemcpyAsync(q.d_fr_rows, rows, nseg * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
+    std::vector<int64_t> ptr(nseg + 1);
+    const bool keep = (flags & PM_FR_KEEP) != 0;
+    const uint64_t by_rules = (uint64_t)nseg * o->flow_rules.nrules, by_events = (uint64_t)nevents * o->flow_rules_fanout;
+    bool dry = q.cap_rl_hits < std::min(by_rules, by_events);  // the hits may not fit: count them first
+    for (;;) {
+        const hipError_t e = pm_launch_flow_rules(q.d_bs_in, nevents, d_cursor, q.d_offs, (int64_t)nseg, o->flow_rules,
+                                                  q.d_fr_sets, (int64_t)nrows, rows ? q.d_fr_rows : nullptr, keep || dry,
+                                                  q.d_rl_hits, q.cap_rl_hits, q.d_bs_ptr, q.d_bs_scr, o->num_cu, q.s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(q.s);
+            std::snprintf(g_err, sizeof(g_err), "flow rules launch: %s", hipGetErrorString(e));
+            return -3;
+        }
+        PM_CHECK(hipMemcpyAsync(ptr.data(), q.d_bs_ptr, ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, q.s));
+        PM_CHECK(hipStreamSynchronize(q.s));
+        if (!dry) break;
+        dry = false;
+        if ((size_t)ptr[nseg] <= q.cap_rl_hits && keep) break;  // the dry call was the call asked for
+        stage_grow((void**)&q.d_rl_hits, nullptr, sizeof(uint64_t), q.cap_rl_hits, (size_t)ptr[nseg]);
+    }
+    const size_t total = (size_t)ptr[nseg];
+    std::vector<uint64_t> hv(total);
+    if (total) PM_CHECK(hipMemcpyAsync(hv.data(), q.d_rl_hits, total * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    if (nwords && !keep)
+        PM_CHECK(hipMemcpyAsync(sets, q.d_fr_sets, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    PM_CHECK(hipStreamSynchronize(q.s));
+    par_range(nseg, (size_t)1 << 12, [&](size_t lo, size_t hi) {
+        for (size_t j = lo; j < hi; ++j) std::sort(hv.begin() + ptr[j], hv.begin() + ptr[j + 1]);
+    });
+    std::memcpy(rule_ptr, ptr.data(), ptr.size() * sizeof(int64_t));
+    if (hits_cap && total) std::memcpy(hits, hv.data(), std::min(hits_cap, total) * sizeof(uint64_t));
+    return 0;
+}
+
 int pm_hip_score_device(void* obj, const uint32_t* d_algo, const uint32_t* d_real, int64_t n,
                         unsigned long long* d_counts, void* hip_stream) {
     PmHip* o = as(obj);
@@ -2790,6 +3007,8 @@ size_t pm_hip_scratch_bytes(void* obj) {
     if (o->batch.d_bs_ptr) b += o->batch.cap_bs_ptr * sizeof(int64_t);
     if (o->batch.d_bs_scr) b += o->batch.cap_bs_scr;
     if (o->batch.d_rl_hits) b += o->batch.cap_rl_hits * sizeof(uint64_t);
+    if (o->batch.d_fr_sets) b += o->batch.cap_fr_sets * sizeof(uint64_t);
+    if (o->batch.d_fr_rows) b += o->batch.cap_fr_rows * sizeof(int64_t);
     return b;
 }
 

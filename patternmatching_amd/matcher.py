@@ -238,6 +238,71 @@ def rules_by_stream_host(events, offsets, rules, hits_cap=None):
     return ptr, hits[:min(len(hits), int(ptr[-1]))]
 
 
+FLOW_RULES_KEEP = 1  # PM_FLOW_RULES_KEEP: report the hits, leave the flows' sets as they are
+
+
+def _flow_rules_host_args(offsets, sets, rows):
+    """The host arrays of a flow-rules call: (offsets int64, sets -- the
+    caller's own (nrows, W) u64 array, updated in place --, rows int64 or
+    None, rule_ptr int64)."""
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offs.ndim != 1 or offs.size < 1:
+        raise ValueError("offsets: nseg + 1 values")
+    if not (isinstance(sets, np.ndarray) and sets.dtype == np.uint64 and sets.ndim == 2 and sets.flags.c_contiguous
+            and sets.flags.writeable):
+        raise ValueError("sets: a writeable C-contiguous (nrows, W) uint64 array (it is updated in place)")
+    if rows is not None:
+        rows = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows.shape != (offs.size - 1,):
+            raise ValueError("rows: one row index per stream")
+    return offs, sets, rows, np.zeros(offs.size, dtype=np.int64)
+
+
+def flow_rule_bits_host(rules, npat):
+    """pm_flat_flow_rule_bits: (bit_by_gid u32 of npat + 1 with 0xFFFFFFFF for
+    a gid that no term names, K): the bit of a gid is its rank among the
+    distinct gids of all terms, ascending.  rules as pack_rules takes them, or
+    its pair."""
+    tptr, terms = rules if isinstance(rules, tuple) else pack_rules(rules)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    bits = np.zeros(npat + 1, dtype=np.uint32)
+    k = ctypes.c_uint32()
+    rc = load().pm_flat_flow_rule_bits(tptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p), len(tptr) - 1, npat,
+                                       bits.ctypes.data_as(u32p), ctypes.byref(k))
+    if rc != 0:
+        raise ValueError(f"pm_flat_flow_rule_bits: bad arguments ({rc})")
+    return bits, int(k.value)
+
+
+def flow_rules_host(events, offsets, rules, sets, rows=None, keep=False):
+    """pm_flat_flow_rules, the host twin of HipMatcher.flow_rules (no matcher,
+    no device): (rule_ptr int64 of nseg + 1, hits u64 of position << 24 |
+    rule) with each stream's range ascending: the rules whose conjunction
+    became true in this call, given the terms each flow carries in its row of
+    sets ((nrows, W) u64, W = max(1, ceil(K / 64)) for the K distinct gids of
+    the rules' terms).  rows[j] is the row of stream j (None: row j).  sets is
+    updated in place unless keep.  rules as pack_rules takes them, or its
+    pair."""
+    ev = np.ascontiguousarray(events, dtype=np.uint64).ravel()
+    offs, sets, rows, ptr = _flow_rules_host_args(offsets, sets, rows)
+    tptr, terms = rules if isinstance(rules, tuple) else pack_rules(rules)
+    u64p, i64p, u32p = (ctypes.POINTER(t) for t in (ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32))
+
+    def call(flags, hits):
+        rc = load().pm_flat_flow_rules(ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p), offs.size - 1,
+                                       tptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p), len(tptr) - 1,
+                                       sets.ctypes.data_as(u64p), sets.shape[0], sets.shape[1],
+                                       None if rows is None else rows.ctypes.data_as(i64p), flags,
+                                       hits.ctypes.data_as(u64p), len(hits), ptr.ctypes.data_as(i64p))
+        if rc != 0:
+            raise ValueError(f"pm_flat_flow_rules: bad arguments ({rc})")
+    # the hits are not bounded by the events and a committing call cannot be repeated: count them first
+    call(FLOW_RULES_KEEP, np.empty(0, dtype=np.uint64))
+    hits = np.empty(int(ptr[-1]), dtype=np.uint64)
+    call(FLOW_RULES_KEEP if keep else 0, hits)
+    return ptr, hits[:int(ptr[-1])]
+
+
 class FlowTable:
     """The carried states of many live flows over one matcher (ac / auto
     kinds): a dict of flow key -> flow state, and one flow call
@@ -250,12 +315,22 @@ class FlowTable:
     A key seen for the first time starts a fresh flow.  A key may appear once
     per scan(): two packets of one flow are concatenated by the caller.
     Beside the state the table keeps the bytes each flow has had, which
-    scan_windows() counts the patterns' windows from."""
+    scan_windows() counts the patterns' windows from.
+
+    scan_rules() gives the flow rules (HipMatcher.set_flow_rules) that fire
+    in each packet: rules whose terms lie in different packets of a flow.
+    For it the table keeps each flow's set of carried terms (rule_sets: W u64
+    words per flow, HipMatcher.flow_rule_words) and the bytes the flow had
+    when scan_rules() last saw it (rule_bytes).  A flow is followed by
+    scan_rules() from its first byte or not at all."""
 
     def __init__(self, matcher):
         self.matcher = matcher
         self.states = {}
         self.bytes = {}  # flow key -> the bytes the flow has had (scan_windows' positions)
+        # scan_rules: the carried terms of each flow, and the bytes it saw
+        self.rule_sets = {}
+        self.rule_bytes = {}
         # scan_nocase: the folded automaton's states, the case histories, and the bytes it saw
         self.nocase_states = {}
         self.nocase_case = {}
@@ -355,6 +430,51 @@ class FlowTable:
             self.nocase_bytes[k] = self.bytes[k]
         return _split_events(pos, codes, offs)
 
+    def scan_rules(self, packets):
+        """packets: a list of (key, bytes-like).  Per packet, in order,
+        (positions inside the packet, rule indices) of the flow rules
+        (HipMatcher.set_flow_rules) whose conjunction became true in that
+        packet, ascending by (position, rule): the terms a flow's earlier
+        packets held count, a rule fires at most once per flow, and a negated
+        term seen so far suppresses it.  One read_flows_matches call at
+        flow_rules_min_len() from the flows' states, then flow_rules over the
+        flows' kept sets.  The flows' states and byte counts advance exactly
+        as in scan().  A flow that got bytes through another scan method
+        since scan_rules() last saw it cannot be continued (its set missed
+        their patterns): ValueError; so is a kept set whose length is not the
+        matcher's current flow_rule_words (the rules were replaced)."""
+        keys = [k for k, _ in packets]
+        _unique_keys(keys, "scan_rules")
+        W = self.matcher.flow_rule_words
+        if W == 0:
+            raise ValueError("scan_rules() before the matcher's set_flow_rules()")
+        for k in keys:
+            if self.bytes.get(k, 0) != self.rule_bytes.get(k, 0):
+                raise ValueError(f"flow {k!r} has had {self.bytes.get(k, 0)} bytes but scan_rules() saw "
+                                 f"{self.rule_bytes.get(k, 0)} of them")
+            if k in self.rule_sets and len(self.rule_sets[k]) != W:
+                raise ValueError(f"flow {k!r} keeps a set of {len(self.rule_sets[k])} words but the matcher's flow "
+                                 f"rules need {W}")
+        if not packets:
+            return []
+        data, offs = _concat([b for _, b in packets])
+        state = np.array([self.states.get(k, 0) for k in keys], dtype=np.uint32)
+        sets = np.zeros((len(keys), W), dtype=np.uint64)
+        for r, k in enumerate(keys):
+            if k in self.rule_sets:
+                sets[r] = self.rule_sets[k]
+        # read_flows_matches' call, its events kept as they are (position << 24 | gid)
+        ev, state = self.matcher._read_events(data, offs, state, self.matcher.flow_rules_min_len(), all_matches=True)
+        ptr, hits = self.matcher.flow_rules(ev, offs, sets)
+        for r, (k, s) in enumerate(zip(keys, state.tolist())):
+            self.states[k] = s
+            self.rule_sets[k] = sets[r].copy()
+        self._advance(keys, offs)
+        for k in keys:
+            self.rule_bytes[k] = self.bytes[k]
+        hpos, rule = unpack_events(hits)
+        return [(hpos[ptr[j]:ptr[j + 1]] - offs[j], rule[ptr[j]:ptr[j + 1]]) for j in range(len(packets))]
+
     def _advance(self, keys, offs):
         for k, n in zip(keys, np.diff(offs).tolist()):
             self.bytes[k] = self.bytes.get(k, 0) + n
@@ -379,6 +499,8 @@ class FlowTable:
         self.nocase_states.pop(key, None)
         self.nocase_case.pop(key, None)
         self.nocase_bytes.pop(key, None)
+        self.rule_sets.pop(key, None)
+        self.rule_bytes.pop(key, None)
 
     def __len__(self):
         return len(self.states)
@@ -832,6 +954,86 @@ class HipMatcher:
         ptr, hits = self.rules_by_stream(ev, offs)
         pos, rule = unpack_events(hits)
         return [(pos[ptr[j]:ptr[j + 1]] - offs[j], rule[ptr[j]:ptr[j + 1]]) for j in range(len(buffers))]
+
+    # --- flow rules: rules over a set per flow, carried from call to call ------
+    def set_flow_rules(self, rules, fast=None):
+        """pm_hip_set_flow_rules: a rule set of its own for flow_rules(), in
+        set_rules' form (set_rules and its rules are not touched).  fast[r]
+        only decides which term of rule r is tested first.  After compile(); a
+        later call replaces the set (no flow-rules call may be in flight), and
+        with it the bits and possibly the words of a flow's set."""
+        ptr, terms = pack_rules(rules, fast)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self.lib.pm_hip_set_flow_rules(self.obj, ptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
+                                                   len(ptr) - 1))
+
+    def flow_rule_count(self):
+        """pm_hip_flow_rule_count: the flow rules set (0 before set_flow_rules)."""
+        return int(self.lib.pm_hip_flow_rule_count(self.obj))
+
+    def flow_rules_min_len(self):
+        """pm_hip_flow_rules_min_len: the length of the shortest pattern any
+        term names: the largest min_len a scan may use for exact hits (0
+        before set_flow_rules)."""
+        return int(self.lib.pm_hip_flow_rules_min_len(self.obj))
+
+    @property
+    def flow_rule_words(self):
+        """pm_hip_flow_rule_words: W, the u64 words of one flow's set (0
+        before set_flow_rules)."""
+        return int(self.lib.pm_hip_flow_rule_words(self.obj))
+
+    def flow_rule_bit(self, gid):
+        """pm_hip_flow_rule_bit: the bit of gid in a flow's set (word bit >>
+        6, bit bit & 63), or -1 where no term names it."""
+        return int(self.lib.pm_hip_flow_rule_bit(self.obj, int(gid)))
+
+    def flow_rules_scratch_bytes(self, cap, nseg):
+        """pm_hip_flow_rules_scratch_bytes: the device scratch, in bytes, that
+        flow_rules_device needs for a list of cap slots over nseg streams."""
+        b = self.lib.pm_hip_flow_rules_scratch_bytes(cap, nseg)
+        if b == ctypes.c_size_t(-1).value:
+            raise ValueError("flow_rules_scratch_bytes: cap <= 2^40, 0 <= nseg < 2^31")
+        return b
+
+    def flow_rules_device(self, d_events_ptr, cap, d_nevents_ptr, d_offsets_ptr, nseg, d_sets_ptr, nrows, d_rows_ptr,
+                          flags, d_hits_ptr, hits_cap, d_rule_ptr_ptr, d_scratch_ptr, scratch_bytes, stream_ptr):
+        """pm_hip_flow_rules_device: behind a flow scan's list (the arguments
+        of rules_by_stream_device), the flow rules whose conjunction became
+        true in this call's bytes, given the terms each flow carries in its
+        row of the nrows x flow_rule_words u64 at d_sets_ptr (d_rows_ptr:
+        nseg int64 row indices, or None for row j); then this call's terms
+        are OR-ed into the rows, unless flags holds FLOW_RULES_KEEP.
+        Enqueued on stream_ptr, no synchronize."""
+        rc = self.lib.pm_hip_flow_rules_device(self.obj, d_events_ptr, cap, d_nevents_ptr, d_offsets_ptr, nseg,
+                                               d_sets_ptr, nrows, d_rows_ptr, flags, d_hits_ptr, hits_cap,
+                                               d_rule_ptr_ptr, d_scratch_ptr, scratch_bytes, stream_ptr)
+        self._check(rc)
+
+    def flow_rules(self, events, offsets, sets, rows=None, keep=False):
+        """pm_hip_flow_rules: host arrays through the device call: (rule_ptr
+        int64 of nseg + 1, hits u64), stream j's hits hits[ptr[j]:ptr[j+1]]
+        ascending, each position << 24 | rule.  sets is a C-contiguous
+        (nrows, flow_rule_words) u64 array, a row per flow, updated in place
+        unless keep; rows[j] is the row of stream j (None: row j).  events
+        come from an all-matches flow scan that continued the same flows, at
+        a min_len <= flow_rules_min_len(), with a cap that held the list."""
+        ev = np.ascontiguousarray(events, dtype=np.uint64).ravel()
+        offs, sets, rows, ptr = _flow_rules_host_args(offsets, sets, rows)
+        u64p, i64p = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64)
+        if self.flow_rule_words and sets.shape[1] != self.flow_rule_words:  # (0: the call says what is missing)
+            raise ValueError(f"sets: {self.flow_rule_words} words per row, not {sets.shape[1]}")
+
+        def call(flags, hits):
+            self._check(self.lib.pm_hip_flow_rules(self.obj, ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p),
+                                                   offs.size - 1, sets.ctypes.data_as(u64p), sets.shape[0],
+                                                   None if rows is None else rows.ctypes.data_as(i64p), flags,
+                                                   hits.ctypes.data_as(u64p), len(hits), ptr.ctypes.data_as(i64p)))
+        # the hits are not bounded by the events and a committing call cannot be repeated: count them first
+        call(FLOW_RULES_KEEP, np.empty(0, dtype=np.uint64))
+        hits = np.empty(int(ptr[-1]), dtype=np.uint64)
+        call(FLOW_RULES_KEEP if keep else 0, hits)
+        return ptr, hits[:int(ptr[-1])]
 
     # --- pattern groups: a group mask per pattern and one per stream --------
     def set_groups(self, masks):
