@@ -909,6 +909,136 @@ int pm_flat_flow_rules(const uint64_t* events, size_t nevents, const int64_t* of
                        size_t words, const int64_t* rows, uint32_t flags, uint64_t* hits, size_t hits_cap,
                        int64_t* rule_ptr);
 
+/*
+ * Ordered rules: rules whose terms must follow one another, at a distance
+ * (Snort's relative content: content:"A"; content:"B"; distance:N;).  The
+ * rules above are unordered sets; here a positive term may have to begin at
+ * least d bytes after the term before it has ended.
+ * An event position << 24 | gid says that pattern gid, of L(gid) bytes, ends
+ * at buffer byte position: the occurrence covers [position - L + 1, position].
+ * An ordered rule is a rule of pm_hip_set_rules (1 to 64 terms; bits 0-23 the
+ * gid, PM_RULE_NEGATED, PM_RULE_FAST) and a parallel uint32_t gaps[], one
+ * value per term:
+ *   - PM_SEQ_FREE (0xFFFFFFFF): the term is as in the rules above: it may lie
+ *     anywhere in the stream;
+ *   - d in [0, 0x7FFFFFFF]: the term FOLLOWS the nearest positive term listed
+ *     before it in the rule (negated terms in between are skipped).  For a
+ *     term t that follows u, the occurrence chosen for t must begin at least d
+ *     bytes after the one chosen for u has ended: p_t - L_t + 1 >= p_u + 1 + d,
+ *     that is p_t >= p_u + d + L_t.  d = 0 is Snort's distance:0.
+ * Terms linked this way form chains; a free positive term starts a chain,
+ * possibly of length 1.
+ * Firing.  The rule fires in a stream iff some choice of one occurrence inside
+ * the stream per positive term satisfies every link, and no negated term's
+ * gid has an occurrence in the stream.  The position of the hit is the
+ * smallest, over all valid choices, of the largest chosen position: the byte
+ * at which the stream's prefix first satisfies the positive part; negations
+ * do not move it.  A hit is position << 24 | rule as above; the output is the
+ * rules call's CSR form (d_rule_ptr[nseg + 1], exact whatever hits_cap is), a
+ * pure function of the used events, the offsets and the rules.  With every
+ * gap PM_SEQ_FREE the hits are those of pm_hip_rules_by_stream_device.  The
+ * call chooses greedily -- a chain's head at its first position, each follower
+ * at its first position that satisfies the link -- which is exact because
+ * positions grow along a chain and an earlier choice never rules out a later
+ * one (the proof is in DESIGN.md §4, "Ordered rules").
+ * The list has the rules call's preconditions: an all-matches form, at a
+ * min_len <= pm_hip_seq_rules_min_len, with a cap that held the list.
+ * Out of scope: an upper bound on a link (Snort's within: the greedy choice is
+ * not exact for it; an exact answer needs the feasible set per chain level or
+ * backtracking), negative distances, relative negated terms, and flows: like
+ * the rules call this one knows no flows and carries no chain from one packet
+ * to the next.
+ * pm_hip_set_seq_rules(obj, term_ptr, terms, gaps, nrules): term_ptr and terms
+ * as pm_hip_set_rules takes them, gaps parallel to terms.  After compile()
+ * only: -1 before.  It runs every check of pm_hip_set_rules, with these
+ * differences and additions (-2 with one message naming every constraint;
+ * nothing changes on an error): a NULL gaps; a gap on a negated term; a gap on
+ * a rule's first positive term; a gap in [0x80000000, 0xFFFFFFFE]; a gid may
+ * occur more than once among a rule's positive terms, every occurrence after
+ * the first being a following term (A ... A); a gid in two free positive
+ * terms and a gid both positive and negated are rejected.  The anchor is
+ * chosen as in pm_hip_set_rules: the PM_RULE_FAST term, else the positive term
+ * with the longest pattern, ties going to the smaller gid.  The rule set is
+ * the object's own: pm_hip_set_rules and pm_hip_set_flow_rules do not see it
+ * and are not touched.  Its device tables (the inverted index gid -> the rules
+ * anchored at it, and per rule a record {gid | flags, gap, L} per term, the
+ * positive ones in listed order, then the negated ones) are counted in
+ * pm_hip_table_bytes and replaced by a later call after a device synchronize:
+ * no ordered-rules call may be in flight.
+ * pm_hip_seq_rule_count: the rules set (0 before).  pm_hip_seq_rules_min_len:
+ * the length of the shortest pattern any term names (0 before).
+ * pm_hip_seq_rules_by_stream_device: the arguments, the output and the
+ * guarantees of pm_hip_rules_by_stream_device: it allocates nothing, runs
+ * asynchronously on hip_stream with no host synchronize inside (it may be
+ * captured; the list's cursor and the work list's length are read on the
+ * device, and the work list's cursor is reset inside the call), and asks the
+ * resident read_block server to leave the device first.  Scratch comes from
+ * the caller, 16-byte aligned, pm_hip_seq_rules_scratch_bytes(cap, nseg) bytes
+ * exactly:
+ *     24 T + r16(8 (T + 1)) + r16(8 cap) + r16(4 (cap / 17 + 1)) + 16
+ *       + r16(8 ceil(T / 1024)) + r16(8 nseg) + r16(8 ceil(nseg / 1024))
+ * T = the power of two >= max(2 cap, 64): the table (a key, a smallest
+ * position and a count per slot), the slots' ranges, every used event's
+ * position grouped by slot and sorted inside a slot, the work list of the
+ * slots with more than 16 positions and its cursor, the block sums of the
+ * scan over the slots, the streams' counts and the block sums of the scan
+ * over them; (size_t)-1 for arguments the call would reject.
+ * Returns 0; -1 before compile(); -2 bad arguments, the rules call's cases; -10
+ * pm_hip_set_seq_rules was not called (whether or not pm_hip_set_rules was);
+ * -3 launch error.  Nothing is launched or written when a check fails.  nseg
+ * == 0: returns 0 and launches nothing.  cap == 0 with nseg > 0: an all-zero
+ * d_rule_ptr.
+ * Memory safety does not depend on the data: beyond the rules call's clamps a
+ * slot's range is clamped into [0, cap] and to begin <= end, a position is
+ * stored below cap only, a work-list entry is tested against T, and a
+ * bisection stays inside its clamped range; garbage offsets or events give
+ * unspecified hits, never an access outside the arrays named here.
+ * Sorting.  A slot's range of at most 16 positions is sorted by one lane; a
+ * longer one by one workgroup with a bitonic network, in LDS up to 4,096
+ * positions, beyond that in parts of 4,096 in LDS and merges whose wide steps
+ * run in global memory: O(m log^2 m) for m positions.  The worst case is one
+ * pattern ending at every byte of one long stream: all of the list in one
+ * range, sorted by one workgroup: 116 ms for 2^20 positions, where the same
+ * events in ranges of 16 to 4,096 take 0.5-1.1 ms.
+ * Measured (the rules call's cells, lists and 10,000 rules, snort;
+ * profiles/seqrules/): 0.084-0.097 ms on random ASCII and 6.9-7.3 ms on the
+ * lines stream, 1.8-1.9x and 2.7-3.7x the rules call on the same list (its
+ * own spread: 1.000-1.088), the same with every gap free and with every later
+ * term at distance 0: the price is the index, not the links (DESIGN.md §4,
+ * "Ordered rules").
+ * pm_hip_seq_rules_by_stream: the host form, as pm_hip_rules_by_stream: host
+ * arrays staged on the object's batch stream, the device call (a second time
+ * where its hits array was too short), each stream's range sorted ascending.
+ * pm_flat_seq_rule_tables, pm_flat_seq_rules_by_stream: the host alone, no
+ * handle and no device; they set no message.  pm_flat_seq_rule_tables runs
+ * every check of pm_hip_set_seq_rules (pattern_len: npat + 1 lengths by gid,
+ * [0] == 0) and returns pm_flat_rule_tables' outputs; 0, or -2 with nothing
+ * written.  pm_flat_seq_rules_by_stream is the twin of the device call over
+ * host arrays, each range sorted ascending: greedy over the sorted
+ * occurrences of every (stream, gid), with an index of its own and no
+ * anchors; it needs pattern_len for the links and runs the same checks; 0, or
+ * -2 with nothing written.
+ */
+#define PM_SEQ_FREE 0xFFFFFFFFu
+int pm_hip_set_seq_rules(void* obj, const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
+                         size_t nrules);
+size_t pm_hip_seq_rule_count(void* obj);
+uint32_t pm_hip_seq_rules_min_len(void* obj);
+size_t pm_hip_seq_rules_scratch_bytes(uint64_t cap, int64_t nseg);
+int pm_hip_seq_rules_by_stream_device(void* obj, const uint64_t* d_events, uint64_t cap,
+                                      const unsigned long long* d_nevents, const int64_t* d_offsets, int64_t nseg,
+                                      uint64_t* d_hits, uint64_t hits_cap, int64_t* d_rule_ptr, void* d_scratch,
+                                      size_t scratch_bytes, void* hip_stream);
+int pm_hip_seq_rules_by_stream(void* obj, const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                               uint64_t* hits, size_t hits_cap, int64_t* rule_ptr);
+int pm_flat_seq_rule_tables(const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps, size_t nrules,
+                            const uint32_t* pattern_len, size_t npat, uint32_t* anchor_ptr_out,
+                            uint32_t* anchor_rules_out, uint32_t* anchor_term_out);
+int pm_flat_seq_rules_by_stream(const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                                const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps, size_t nrules,
+                                const uint32_t* pattern_len, size_t npat, uint64_t* hits, size_t hits_cap,
+                                int64_t* rule_ptr);
+
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,
  * PatternsTree.c:485-494): per position, equal -> success; d_algo's pattern

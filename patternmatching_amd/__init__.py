@@ -44,6 +44,11 @@ interface:
                     of HipMatcher.set_flow_rules / flow_rules /
                     flow_rules_device and FlowTable.scan_rules;
                     flow_rule_bits_host gives the sets' bit numbering)
+    seq_rules_by_stream_host    ordered rules (pack_seq_rules: terms that must
+                    follow one another at a distance, Snort's distance:N)
+                    without a device (the host twin of
+                    HipMatcher.set_seq_rules / seq_rules_by_stream /
+                    seq_rules_by_stream_device / read_many_seq_rules)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401
@@ -59,6 +64,9 @@ from .matcher import (  # noqa: F401
     rules_by_stream_host,
     flow_rules_host,
     flow_rule_bits_host,
+    pack_seq_rules,
+    seq_rules_by_stream_host,
+    SEQ_FREE,
     FLOW_RULES_KEEP,
     RULE_NEGATED,
     RULE_FAST,
@@ -70,4 +78,5 @@ from .matcher import (  # noqa: F401
 
 __all__ = ["load", "Dictionary", "HipMatcher", "FlowTable", "gen_stream", "batch_offsets", "unpack_events", "parse_line",
            "events_by_stream_host", "BY_STREAM_UNIQUE", "pack_rules", "rules_by_stream_host",
-           "flow_rules_host", "flow_rule_bits_host", "FLOW_RULES_KEEP", "RULE_NEGATED", "RULE_FAST", "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]
+           "flow_rules_host", "flow_rule_bits_host", "pack_seq_rules", "seq_rules_by_stream_host", "SEQ_FREE",
+           "FLOW_RULES_KEEP", "RULE_NEGATED", "RULE_FAST", "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]

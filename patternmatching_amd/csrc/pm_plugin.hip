@@ -40,6 +40,7 @@
 #include "pm_kernels.h"
 #include "pm_flowrules.h"
 #include "pm_rules.h"
+#include "pm_seqrules.h"
 #include "pm_streamgen.h"
 
 #ifndef PM_NT_IDS
@@ -345,6 +346,11 @@ struct PmHip {
     std::vector<uint32_t> flow_rule_bits;  // host copy of gid_bit (pm_hip_flow_rule_bit)
     std::vector<void*> flow_rules_allocs;
     size_t flow_rules_bytes = 0;
+    // ordered rules (pm_hip_set_seq_rules): a rule set of their own, held the same way
+    PmSeqRulesDev seq_rules{};
+    uint32_t seq_rules_min_len = 0;
+    std::vector<void*> seq_rules_allocs;
+    size_t seq_rules_bytes = 0;
     std::string cache_dir;  // compiled-image cache (else $PM_IMAGE_CACHE)
     bool cache_hit = false;
     std::vector<void*> allocs;
@@ -1441,6 +1447,7 @@ void pm_hip_free(void* obj) {
     for (void* p : o->nc.allocs) (void)hipFree(p);
     for (void* p : o->rules_allocs) (void)hipFree(p);
     for (void* p : o->flow_rules_allocs) (void)hipFree(p);
+    for (void* p : o->seq_rules_allocs) (void)hipFree(p);
     if (o->spill) (void)hipFree(o->spill);
     for (StreamSpill& x : o->sspill) {
         if (x.buf) (void)hipFree(x.buf);
@@ -2935,6 +2942,174 @@ int pm_hip_flow_rules(void* obj, const uint64_t* events, size_t nevents, const i
     if (total) PM_CHECK(hipMemcpyAsync(hv.data(), q.d_rl_hits, total * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
     if (nwords && !keep)
         PM_CHECK(hipMemcpyAsync(sets, q.d_fr_sets, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    PM_CHECK(hipStreamSynchronize(q.s));
+    par_range(nseg, (size_t)1 << 12, [&](size_t lo, size_t hi) {
+        for (size_t j = lo; j < hi; ++j) std::sort(hv.begin() + ptr[j], hv.begin() + ptr[j + 1]);
+    });
+    std::memcpy(rule_ptr, ptr.data(), ptr.size() * sizeof(int64_t));
+    if (hits_cap && total) std::memcpy(hits, hv.data(), std::min(hits_cap, total) * sizeof(uint64_t));
+    return 0;
+}
+
+// ---- ordered rules: terms that follow one another at a distance (pm_seqrules.hip) ----
+// The tables of pm_seq_rules_image on the device, in allocations of their own,
+// replaced like the rules' tables.  pm_hip_set_rules, pm_hip_set_flow_rules and
+// their tables are not touched.
+int pm_hip_set_seq_rules(void* obj, const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
+                         size_t nrules) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    PmSeqRulesImage img;
+    const size_t npat = o->gids.len.empty() ? 0 : o->gids.len.size() - 1;
+    if (o->gids.len.empty() || pm_seq_rules_image(term_ptr, terms, gaps, nrules, o->gids.len.data(), npat, img)) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (term_ptr, terms and gaps required, 1 <= nrules <= 2^24, term_ptr from 0, 1 to 64 "
+                      "terms per rule, a positive term in each, every gid a pattern's, no bits but the gid, "
+                      "PM_RULE_NEGATED and PM_RULE_FAST, at most one PM_RULE_FAST per rule, none on a negated term; a "
+                      "gap is PM_SEQ_FREE or at most 0x7FFFFFFF, PM_SEQ_FREE on a negated term and on the first "
+                      "positive term; a gid twice among the positive terms only as a following term, never twice "
+                      "free, never both positive and negated)");
+        return -2;
+    }
+    PM_CHECK(hipSetDevice(o->device));
+    if (!o->seq_rules_allocs.empty()) {
+        PM_CHECK(hipDeviceSynchronize());  // the caller has no ordered-rules call in flight; nor has this object now
+        for (void* p : o->seq_rules_allocs) PM_CHECK(hipFree(p));
+        o->seq_rules_allocs.clear();
+        o->table_bytes -= o->seq_rules_bytes;
+        o->seq_rules_bytes = 0;
+        o->seq_rules = PmSeqRulesDev();
+    }
+    auto up = [&](const std::vector<uint32_t>& v) {
+        void* p = nullptr;
+        const size_t bytes = v.size() * sizeof(uint32_t);
+        PM_CHECK(hipMalloc(&p, bytes));
+        PM_CHECK(hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice));
+        o->seq_rules_allocs.push_back(p);
+        o->seq_rules_bytes += bytes;
+        o->table_bytes += bytes;
+        return (const uint32_t*)p;
+    };
+    PmSeqRulesDev d;
+    d.anchor_ptr = up(img.anchor_ptr);
+    d.anchor_rules = up(img.anchor_rules);
+    d.rterm_ptr = up(img.rterm_ptr);
+    d.recs = up(img.recs);
+    d.ngid = (uint32_t)(npat + 1);
+    d.nrules = (uint32_t)nrules;
+    d.nterms = (uint32_t)(img.recs.size() / PM_SQ_REC);
+    o->seq_rules = d;
+    o->seq_rules_min_len = img.min_len;
+    return 0;
+}
+
+size_t pm_hip_seq_rule_count(void* obj) { return as(obj)->seq_rules.nrules; }
+
+uint32_t pm_hip_seq_rules_min_len(void* obj) {
+    PmHip* o = as(obj);
+    return o->seq_rules.nrules ? o->seq_rules_min_len : 0u;
+}
+
+// Every check, then the passes; nothing is written before all of them pass.
+int pm_hip_seq_rules_by_stream_device(void* obj, const uint64_t* d_events, uint64_t cap,
+                                      const unsigned long long* d_nevents, const int64_t* d_offsets, int64_t nseg,
+                                      uint64_t* d_hits, uint64_t hits_cap, int64_t* d_rule_ptr, void* d_scratch,
+                                      size_t scratch_bytes, void* hip_stream) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    bool ok = nseg >= 0 && nseg < PM_BS_MAX_NSEG && cap <= PM_BS_MAX_CAP && !misaligned(d_events, 8) &&
+              !misaligned(d_nevents, 8) && !misaligned(d_offsets, 8) && !misaligned(d_hits, 8) &&
+              !misaligned(d_rule_ptr, 8) && !misaligned(d_scratch, 16) && !(d_hits && d_hits == d_events) &&
+              !(cap && !d_events) && !(hits_cap && !d_hits);
+    if (ok && nseg > 0)
+        ok = d_nevents && d_offsets && d_rule_ptr && d_scratch &&
+             scratch_bytes >= pm_seq_rules_layout(cap, nseg).bytes;
+    if (!ok) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (events, nevents, offsets, hits and rule_ptr non-NULL and 8-B aligned, scratch "
+                      "non-NULL and 16-B aligned, 0 <= nseg < 2^31, cap <= 2^40, hits != events, scratch_bytes >= "
+                      "pm_hip_seq_rules_scratch_bytes)");
+        return -2;
+    }
+    if (!o->seq_rules.nrules) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "pm_hip_set_seq_rules was not called: an ordered-rules call needs the rule tables");
+        return -10;
+    }
+    if (nseg == 0) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess) {
+        if (cap == 0)
+            e = hipMemsetAsync(d_rule_ptr, 0, ((size_t)nseg + 1) * sizeof(int64_t), (hipStream_t)hip_stream);
+        else
+            e = pm_launch_seq_rules_by_stream(d_events, cap, d_nevents, d_offsets, nseg, o->seq_rules, d_hits, hits_cap,
+                                              d_rule_ptr, d_scratch, o->num_cu, (hipStream_t)hip_stream);
+    }
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "ordered rules launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    return 0;
+}
+
+// The host form, as pm_hip_rules_by_stream and on its staging: the list, its
+// count and the offsets to the batch staging, the device call, rule_ptr back,
+// then the hits; where the staging's hits array was too short for them it is
+// grown to the exact count and the call repeated.  Each stream's range is
+// sorted here.
+int pm_hip_seq_rules_by_stream(void* obj, const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                               uint64_t* hits, size_t hits_cap, int64_t* rule_ptr) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    if ((nevents && !events) || (nseg && (!offsets || !rule_ptr)) || (hits_cap && !hits) ||
+        nseg >= (size_t)PM_BS_MAX_NSEG || nevents > PM_BS_MAX_CAP || (hits && hits == events)) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (events, offsets, hits and rule_ptr non-NULL, nseg < 2^31, nevents <= 2^40, hits "
+                      "!= events)");
+        return -2;
+    }
+    if (!o->seq_rules.nrules) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "pm_hip_set_seq_rules was not called: an ordered-rules call needs the rule tables");
+        return -10;
+    }
+    if (nseg == 0) return 0;
+    if (nevents == 0) {
+        std::fill(rule_ptr, rule_ptr + nseg + 1, (int64_t)0);
+        return 0;
+    }
+    PM_CHECK(hipSetDevice(o->device));
+    BatchStage& q = o->batch;
+    batch_stage_grow(q, 0, nseg);  // the stream and the offsets
+    stage_grow((void**)&q.d_bs_in, (void**)&q.d_bs_out, sizeof(uint64_t), q.cap_bs, nevents);
+    stage_grow((void**)&q.d_bs_ptr, nullptr, sizeof(int64_t), q.cap_bs_ptr, nseg + 2);  // + the list's cursor
+    stage_grow(&q.d_bs_scr, nullptr, 1, q.cap_bs_scr, pm_seq_rules_layout(nevents, (int64_t)nseg).bytes);
+    stage_grow((void**)&q.d_rl_hits, nullptr, sizeof(uint64_t), q.cap_rl_hits, nevents);
+    unsigned long long* d_cursor = reinterpret_cast<unsigned long long*>(q.d_bs_ptr + nseg + 1);
+    const unsigned long long cursor = nevents;
+    serve_stop(o);  // a device launch wants the whole device
+    PM_CHECK(hipMemcpyAsync(q.d_bs_in, events, nevents * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(d_cursor, &cursor, sizeof(cursor), hipMemcpyHostToDevice, q.s));
+    std::vector<int64_t> ptr(nseg + 1);
+    for (int turn = 0; turn < 2; ++turn) {
+        const hipError_t e =
+            pm_launch_seq_rules_by_stream(q.d_bs_in, nevents, d_cursor, q.d_offs, (int64_t)nseg, o->seq_rules,
+                                          q.d_rl_hits, q.cap_rl_hits, q.d_bs_ptr, q.d_bs_scr, o->num_cu, q.s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(q.s);
+            std::snprintf(g_err, sizeof(g_err), "ordered rules launch: %s", hipGetErrorString(e));
+            return -3;
+        }
+        PM_CHECK(hipMemcpyAsync(ptr.data(), q.d_bs_ptr, ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, q.s));
+        PM_CHECK(hipStreamSynchronize(q.s));
+        if ((size_t)ptr[nseg] <= q.cap_rl_hits) break;  // (the second turn's array holds the first's exact count)
+        stage_grow((void**)&q.d_rl_hits, nullptr, sizeof(uint64_t), q.cap_rl_hits, (size_t)ptr[nseg]);
+    }
+    const size_t total = (size_t)ptr[nseg];
+    std::vector<uint64_t> hv(total);
+    if (total) PM_CHECK(hipMemcpyAsync(hv.data(), q.d_rl_hits, total * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
     PM_CHECK(hipStreamSynchronize(q.s));
     par_range(nseg, (size_t)1 << 12, [&](size_t lo, size_t hi) {
         for (size_t j = lo; j < hi; ++j) std::sort(hv.begin() + ptr[j], hv.begin() + ptr[j + 1]);

@@ -238,6 +238,71 @@ def rules_by_stream_host(events, offsets, rules, hits_cap=None):
     return ptr, hits[:min(len(hits), int(ptr[-1]))]
 
 
+SEQ_FREE = 0xFFFFFFFF  # PM_SEQ_FREE: the term may lie anywhere in the stream
+
+
+def pack_seq_rules(rules, fast=None):
+    """(term_ptr u32 of len(rules) + 1, terms u32, gaps u32): the form that
+    pm_hip_set_seq_rules takes.  A rule is a sequence of (gid, gap) pairs: g
+    a positive term, -g a negated one; gap None for a free term (PM_SEQ_FREE),
+    or d >= 0: the term begins at least d bytes after the positive term listed
+    before it has ended.  fast[r] is the gid of rule r's RULE_FAST term (the
+    first positive term of that gid), or None."""
+    rules = [[tuple(t) for t in r] for r in rules]
+    if fast is not None and len(fast) != len(rules):
+        raise ValueError("fast: one gid or None per rule")
+    ptr = np.zeros(len(rules) + 1, dtype=np.uint32)
+    terms, gaps = [], []
+    for r, rule in enumerate(rules):
+        f = None if fast is None else fast[r]
+        if f is not None and f not in [g for g, _ in rule]:
+            raise ValueError(f"fast[{r}] = {f} is no positive term of rule {r}")
+        for g, gap in rule:
+            g = int(g)
+            if g == 0 or abs(g) >= 1 << EVENT_GID_BITS:
+                raise ValueError(f"rule {r}: a term is a gid in [1, 2^24) or its negative, not {g}")
+            if gap is not None and not 0 <= int(gap) <= 0x7FFFFFFF:
+                raise ValueError(f"rule {r}: a gap is None or a distance in [0, 2^31), not {gap}")
+            if g == f:
+                terms.append(g | RULE_FAST)
+                f = None
+            else:
+                terms.append((-g | RULE_NEGATED) if g < 0 else g)
+            gaps.append(SEQ_FREE if gap is None else int(gap))
+        ptr[r + 1] = len(terms)
+    return ptr, np.asarray(terms, dtype=np.uint32), np.asarray(gaps, dtype=np.uint32)
+
+
+def seq_rules_by_stream_host(events, offsets, rules, pattern_len, hits_cap=None):
+    """pm_flat_seq_rules_by_stream, the host twin of
+    HipMatcher.seq_rules_by_stream (no matcher, no device): (rule_ptr int64 of
+    nseg + 1, hits u64 of position << 24 | rule) with each stream's range
+    ascending; rules as pack_seq_rules takes them, or its (term_ptr, terms,
+    gaps) triple; pattern_len the patterns' lengths by gid ([0] == 0), which
+    the links need."""
+    ev = np.ascontiguousarray(events, dtype=np.uint64).ravel()
+    offs = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offs.ndim != 1 or offs.size < 1:
+        raise ValueError("offsets: nseg + 1 values")
+    tptr, terms, gaps = rules if isinstance(rules, tuple) else pack_seq_rules(rules)
+    plen = np.ascontiguousarray(pattern_len, dtype=np.uint32)
+    u64p, i64p, u32p = (ctypes.POINTER(t) for t in (ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32))
+    ptr = np.zeros(offs.size, dtype=np.int64)
+    hits = np.empty(0 if hits_cap is None else hits_cap, dtype=np.uint64)
+    for _ in range(2):  # the hits are not bounded by the events: the first call counts them
+        rc = load().pm_flat_seq_rules_by_stream(ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p),
+                                                offs.size - 1, tptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
+                                                gaps.ctypes.data_as(u32p), len(tptr) - 1, plen.ctypes.data_as(u32p),
+                                                len(plen) - 1, hits.ctypes.data_as(u64p), len(hits),
+                                                ptr.ctypes.data_as(i64p))
+        if rc != 0:
+            raise ValueError(f"pm_flat_seq_rules_by_stream: bad arguments ({rc})")
+        if hits_cap is not None or len(hits) >= ptr[-1]:
+            break
+        hits = np.empty(int(ptr[-1]), dtype=np.uint64)
+    return ptr, hits[:min(len(hits), int(ptr[-1]))]
+
+
 FLOW_RULES_KEEP = 1  # PM_FLOW_RULES_KEEP: report the hits, leave the flows' sets as they are
 
 
@@ -952,6 +1017,82 @@ class HipMatcher:
         data, offs = _concat(buffers)
         ev, _ = self._read_events(data, offs, None, self.rules_min_len(), all_matches=True)
         ptr, hits = self.rules_by_stream(ev, offs)
+        pos, rule = unpack_events(hits)
+        return [(pos[ptr[j]:ptr[j + 1]] - offs[j], rule[ptr[j]:ptr[j + 1]]) for j in range(len(buffers))]
+
+    # --- ordered rules: terms that follow one another at a distance -------------
+    def set_seq_rules(self, rules, fast=None):
+        """pm_hip_set_seq_rules: a rule set of its own (set_rules and
+        set_flow_rules are not touched).  A rule is a sequence of 1 to 64
+        (gid, gap) pairs as pack_seq_rules takes them: gap None for a free
+        term, d >= 0 for one that begins at least d bytes after the positive
+        term before it has ended (d = 0 is Snort's distance:0); -gid a negated
+        term.  After compile(); a later call replaces the rules (no
+        ordered-rules call may be in flight)."""
+        ptr, terms, gaps = pack_seq_rules(rules, fast)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self.lib.pm_hip_set_seq_rules(self.obj, ptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
+                                                  gaps.ctypes.data_as(u32p), len(ptr) - 1))
+
+    def seq_rule_count(self):
+        """pm_hip_seq_rule_count: the ordered rules set (0 before set_seq_rules)."""
+        return int(self.lib.pm_hip_seq_rule_count(self.obj))
+
+    def seq_rules_min_len(self):
+        """pm_hip_seq_rules_min_len: the length of the shortest pattern any
+        term names: the largest min_len a scan may use for exact hits (0
+        before set_seq_rules)."""
+        return int(self.lib.pm_hip_seq_rules_min_len(self.obj))
+
+    def seq_rules_scratch_bytes(self, cap, nseg):
+        """pm_hip_seq_rules_scratch_bytes: the device scratch, in bytes, that
+        seq_rules_by_stream_device needs for a list of cap slots over nseg
+        streams."""
+        b = self.lib.pm_hip_seq_rules_scratch_bytes(cap, nseg)
+        if b == ctypes.c_size_t(-1).value:
+            raise ValueError("seq_rules_scratch_bytes: cap <= 2^40, 0 <= nseg < 2^31")
+        return b
+
+    def seq_rules_by_stream_device(self, d_events_ptr, cap, d_nevents_ptr, d_offsets_ptr, nseg, d_hits_ptr, hits_cap,
+                                   d_rule_ptr_ptr, d_scratch_ptr, scratch_bytes, stream_ptr):
+        """pm_hip_seq_rules_by_stream_device: the ordered rules that fire in
+        each of the scan's streams; the arguments and the output of
+        rules_by_stream_device, the scratch seq_rules_scratch_bytes(cap, nseg).
+        Enqueued on stream_ptr, no synchronize.  Scan with an all-matches
+        form, at a min_len <= seq_rules_min_len(), with a cap that holds the
+        whole list."""
+        rc = self.lib.pm_hip_seq_rules_by_stream_device(self.obj, d_events_ptr, cap, d_nevents_ptr, d_offsets_ptr,
+                                                        nseg, d_hits_ptr, hits_cap, d_rule_ptr_ptr, d_scratch_ptr,
+                                                        scratch_bytes, stream_ptr)
+        self._check(rc)
+
+    def seq_rules_by_stream(self, events, offsets):
+        """pm_hip_seq_rules_by_stream: host arrays through the device call:
+        (rule_ptr int64 of nseg + 1, hits u64), stream j's hits
+        hits[ptr[j]:ptr[j+1]] ascending, each position << 24 | rule with the
+        position at which the stream's prefix first satisfied the rule's
+        positive part (unpack_events splits them)."""
+        ev, offs, _, ptr = _by_stream_host_args(events, offsets, 0)
+        u64p, i64p = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64)
+        hits = np.empty(max(len(ev), 1), dtype=np.uint64)
+        for _ in range(2):  # the hits are not bounded by the events: rule_ptr[-1] sizes the retry
+            rc = self.lib.pm_hip_seq_rules_by_stream(self.obj, ev.ctypes.data_as(u64p), len(ev),
+                                                     offs.ctypes.data_as(i64p), offs.size - 1,
+                                                     hits.ctypes.data_as(u64p), len(hits), ptr.ctypes.data_as(i64p))
+            self._check(rc)
+            if len(hits) >= ptr[-1]:
+                break
+            hits = np.empty(int(ptr[-1]), dtype=np.uint64)
+        return ptr, hits[:int(ptr[-1])]
+
+    def read_many_seq_rules(self, buffers):
+        """One all-matches batch list call over a list of bytes-like streams at
+        seq_rules_min_len(), then seq_rules_by_stream: per stream, in order,
+        (positions inside the stream, rule indices) of the ordered rules that
+        fire in it, ascending by position."""
+        data, offs = _concat(buffers)
+        ev, _ = self._read_events(data, offs, None, self.seq_rules_min_len(), all_matches=True)
+        ptr, hits = self.seq_rules_by_stream(ev, offs)
         pos, rule = unpack_events(hits)
         return [(pos[ptr[j]:ptr[j + 1]] - offs[j], rule[ptr[j]:ptr[j + 1]]) for j in range(len(buffers))]
 
