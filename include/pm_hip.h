@@ -943,11 +943,52 @@ int pm_flat_flow_rules(const uint64_t* events, size_t nevents, const int64_t* of
  * one (the proof is in DESIGN.md §4, "Ordered rules").
  * The list has the rules call's preconditions: an all-matches form, at a
  * min_len <= pm_hip_seq_rules_min_len, with a cap that held the list.
- * Out of scope: an upper bound on a link (Snort's within: the greedy choice is
- * not exact for it; an exact answer needs the feasible set per chain level or
- * backtracking), negative distances, relative negated terms, and flows: like
+ * Out of scope: negative distances, relative negated terms, and flows: like
  * the rules call this one knows no flows and carries no chain from one packet
  * to the next.
+ * Within: an upper bound on a link.  Beside gaps[] a rule set may carry a
+ * second parallel uint32_t withins[], one value per term:
+ *   - PM_SEQ_FREE: no upper bound; the term is as above;
+ *   - w in [0, 0x7FFFFFFF], on a term t that follows u: the occurrence chosen
+ *     for t must end at most w bytes after the one chosen for u has ended:
+ *     p_t <= p_u + w, beside the lower bound p_t >= p_u + d + L_t.
+ * With d == 0 this is Snort's and Suricata's within:w.  w counts from the end
+ * of u whatever the distance, as Suricata counts it; a front end that counts
+ * within from behind the distance passes d + W.  w == d + L_t places t exactly
+ * d bytes behind u.  A within is accepted only on a following term (one whose
+ * gap is not PM_SEQ_FREE, so never on a negated term); it is rejected where w
+ * < d + L_t, because no occurrence can meet that link (Suricata rejects it
+ * too), and in [0x80000000, 0xFFFFFFFE].  Firing and the hit's position are
+ * as above, "every link" meaning both bounds.  With an upper bound an earlier
+ * choice can rule out a later one and the greedy choice is no longer exact:
+ * a set with at least one bound is evaluated by a walk of its own, which is
+ * exact (level by level, F_0 = occ(t_0) and F_i = {p in occ(t_i): some f in
+ * F_(i-1) has f + d_i + L_i <= p <= f + w_i}; a chain's value is min F_last,
+ * the hit the largest over the chains; the walk and its proof are in DESIGN.md
+ * §4, "The walk with an upper bound").  A set without any bound runs the
+ * greedy kernel as before, and with every within free the hits are the same,
+ * hit for hit.
+ * pm_hip_set_seq_rules_within(obj, term_ptr, terms, gaps, withins, nrules):
+ * pm_hip_set_seq_rules with the bounds; withins == NULL means every value is
+ * PM_SEQ_FREE, and pm_hip_set_seq_rules is this call with NULL.  It sets the
+ * object's one ordered rule set.  The same return codes, the same message
+ * (which names within), the same device synchronize before replacing and the
+ * same accounting in pm_hip_table_bytes; the bounds are one more device array
+ * of a word per term, by record, uploaded only where the set has a bound.
+ * pm_hip_seq_rules_within_run(obj): the longest run of consecutive bounded
+ * links in any rule of the set; 0 where there is no bound and before a set.
+ * The walk keeps one u32 cursor per level of a run in LDS, 256 x 4 x run
+ * bytes per workgroup (at most 63 KiB).  pm_hip_seq_rules_by_stream_device,
+ * pm_hip_seq_rules_by_stream and pm_hip_seq_rules_scratch_bytes keep their
+ * signatures, return codes, scratch formula and guarantees, and honour the
+ * set's bounds.  The walk's loops are bounded by the list's capacity and its
+ * reads by the clamped ranges, as the rest of the call's.
+ * Measured (profiles/within/; DESIGN.md §4, "The walk with an upper bound"): a
+ * set with every later term bounded costs 1.08-1.14x the distance-only set on
+ * random ASCII and 1.22-1.27x on the lines stream (the eval pass alone 2x); an
+ * unbounded set runs in the parent's time.  The worst case is one lane walking
+ * two long ranges whose candidates all fail: 98.6 ms for two ranges of 25,592
+ * positions in one 100 KiB stream.
  * pm_hip_set_seq_rules(obj, term_ptr, terms, gaps, nrules): term_ptr and terms
  * as pm_hip_set_rules takes them, gaps parallel to terms.  After compile()
  * only: -1 before.  It runs every check of pm_hip_set_rules, with these
@@ -1017,11 +1058,27 @@ int pm_flat_flow_rules(const uint64_t* events, size_t nevents, const int64_t* of
  * host arrays, each range sorted ascending: greedy over the sorted
  * occurrences of every (stream, gid), with an index of its own and no
  * anchors; it needs pattern_len for the links and runs the same checks; 0, or
- * -2 with nothing written.
+ * -2 with nothing written.  pm_flat_seq_rule_tables_within and
+ * pm_flat_seq_rules_by_stream_within take withins (NULL: every one free) and
+ * run every check of pm_hip_set_seq_rules_within; the twin does not use the
+ * device's walk: it computes the feasible sets level by level over each
+ * stream's sorted occurrences, per occurrence two bisections in the level
+ * before and a prefix count of that level's feasible flags: O(n log n), no
+ * backtracking.
  */
 #define PM_SEQ_FREE 0xFFFFFFFFu
 int pm_hip_set_seq_rules(void* obj, const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
                          size_t nrules);
+int pm_hip_set_seq_rules_within(void* obj, const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
+                                const uint32_t* withins, size_t nrules);
+uint32_t pm_hip_seq_rules_within_run(void* obj);
+int pm_flat_seq_rule_tables_within(const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
+                                   const uint32_t* withins, size_t nrules, const uint32_t* pattern_len, size_t npat,
+                                   uint32_t* anchor_ptr_out, uint32_t* anchor_rules_out, uint32_t* anchor_term_out);
+int pm_flat_seq_rules_by_stream_within(const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                                       const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
+                                       const uint32_t* withins, size_t nrules, const uint32_t* pattern_len,
+                                       size_t npat, uint64_t* hits, size_t hits_cap, int64_t* rule_ptr);
 size_t pm_hip_seq_rule_count(void* obj);
 uint32_t pm_hip_seq_rules_min_len(void* obj);
 size_t pm_hip_seq_rules_scratch_bytes(uint64_t cap, int64_t nseg);

@@ -65,6 +65,7 @@ from .matcher import (  # noqa: F401
     flow_rules_host,
     flow_rule_bits_host,
     pack_seq_rules,
+    pack_seq_rules_within,
     seq_rules_by_stream_host,
     SEQ_FREE,
     FLOW_RULES_KEEP,
@@ -78,5 +79,6 @@ from .matcher import (  # noqa: F401
 
 __all__ = ["load", "Dictionary", "HipMatcher", "FlowTable", "gen_stream", "batch_offsets", "unpack_events", "parse_line",
            "events_by_stream_host", "BY_STREAM_UNIQUE", "pack_rules", "rules_by_stream_host",
-           "flow_rules_host", "flow_rule_bits_host", "pack_seq_rules", "seq_rules_by_stream_host", "SEQ_FREE",
-           "FLOW_RULES_KEEP", "RULE_NEGATED", "RULE_FAST", "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]
+           "flow_rules_host", "flow_rule_bits_host", "pack_seq_rules", "pack_seq_rules_within",
+           "seq_rules_by_stream_host", "SEQ_FREE", "FLOW_RULES_KEEP", "RULE_NEGATED", "RULE_FAST", "KIND_RT", "KIND_AC",
+           "KIND_AUTO", "LIB_PATH", "CLI_PATH"]

@@ -297,6 +297,15 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
                                           ctypes.POINTER(ctypes.c_int64)]),
     "pm_hip_set_seq_rules": (ctypes.c_int, [c_vp, c_u32p, c_u32p, c_u32p, ctypes.c_size_t]),
+    "pm_hip_set_seq_rules_within": (ctypes.c_int, [c_vp, c_u32p, c_u32p, c_u32p, c_u32p, ctypes.c_size_t]),
+    "pm_hip_seq_rules_within_run": (ctypes.c_uint32, [c_vp]),
+    "pm_flat_seq_rule_tables_within": (ctypes.c_int, [c_u32p, c_u32p, c_u32p, c_u32p, ctypes.c_size_t, c_u32p,
+                                                      ctypes.c_size_t, c_u32p, c_u32p, c_u32p]),
+    "pm_flat_seq_rules_by_stream_within": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+                                                          ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, c_u32p,
+                                                          c_u32p, c_u32p, c_u32p, ctypes.c_size_t, c_u32p,
+                                                          ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64),
+                                                          ctypes.c_size_t, ctypes.POINTER(ctypes.c_int64)]),
     "pm_hip_seq_rule_count": (ctypes.c_size_t, [c_vp]),
     "pm_hip_seq_rules_min_len": (ctypes.c_uint32, [c_vp]),
     "pm_hip_seq_rules_scratch_bytes": (ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_int64]),

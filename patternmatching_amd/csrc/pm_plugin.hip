@@ -49,7 +49,7 @@
 
 namespace {
 
-thread_local char g_err[512] = "";
+thread_local char g_err[768] = "";  // (the ordered rules' one message names every constraint: 612 bytes)
 
 [[noreturn]] void fatal(const char* what, hipError_t e) {
     std::fprintf(stderr, "pm_hip: %s failed: %s\n", what, hipGetErrorString(e));
@@ -2957,18 +2957,27 @@ int pm_hip_flow_rules(void* obj, const uint64_t* events, size_t nevents, const i
 // their tables are not touched.
 int pm_hip_set_seq_rules(void* obj, const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
                          size_t nrules) {
+    return pm_hip_set_seq_rules_within(obj, term_ptr, terms, gaps, nullptr, nrules);
+}
+
+// With the links' upper bounds (NULL: none).  The bounds are one more table, by
+// record, uploaded only where the set has one.
+int pm_hip_set_seq_rules_within(void* obj, const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
+                                const uint32_t* withins, size_t nrules) {
     PmHip* o = as(obj);
     if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
     PmSeqRulesImage img;
     const size_t npat = o->gids.len.empty() ? 0 : o->gids.len.size() - 1;
-    if (o->gids.len.empty() || pm_seq_rules_image(term_ptr, terms, gaps, nrules, o->gids.len.data(), npat, img)) {
+    if (o->gids.len.empty() ||
+        pm_seq_rules_image_within(term_ptr, terms, gaps, withins, nrules, o->gids.len.data(), npat, img)) {
         std::snprintf(g_err, sizeof(g_err),
                       "bad arguments (term_ptr, terms and gaps required, 1 <= nrules <= 2^24, term_ptr from 0, 1 to 64 "
                       "terms per rule, a positive term in each, every gid a pattern's, no bits but the gid, "
                       "PM_RULE_NEGATED and PM_RULE_FAST, at most one PM_RULE_FAST per rule, none on a negated term; a "
                       "gap is PM_SEQ_FREE or at most 0x7FFFFFFF, PM_SEQ_FREE on a negated term and on the first "
                       "positive term; a gid twice among the positive terms only as a following term, never twice "
-                      "free, never both positive and negated)");
+                      "free, never both positive and negated; a within is PM_SEQ_FREE, or on a following term a "
+                      "bound of at least gap + the pattern's length and at most 0x7FFFFFFF)");
         return -2;
     }
     PM_CHECK(hipSetDevice(o->device));
@@ -2998,12 +3007,19 @@ int pm_hip_set_seq_rules(void* obj, const uint32_t* term_ptr, const uint32_t* te
     d.ngid = (uint32_t)(npat + 1);
     d.nrules = (uint32_t)nrules;
     d.nterms = (uint32_t)(img.recs.size() / PM_SQ_REC);
+    if (img.within_run) d.wins = up(img.wins);
+    d.within_run = img.within_run;
     o->seq_rules = d;
     o->seq_rules_min_len = img.min_len;
     return 0;
 }
 
 size_t pm_hip_seq_rule_count(void* obj) { return as(obj)->seq_rules.nrules; }
+
+uint32_t pm_hip_seq_rules_within_run(void* obj) {
+    PmHip* o = as(obj);
+    return o->seq_rules.nrules ? o->seq_rules.within_run : 0u;
+}
 
 uint32_t pm_hip_seq_rules_min_len(void* obj) {
     PmHip* o = as(obj);

@@ -83,11 +83,21 @@ struct PmSeqRulesImage {
     std::vector<uint32_t> rterm_ptr;     // nrules + 1, in records
     std::vector<uint32_t> recs;          // PM_SQ_REC words per term
     uint32_t min_len = 0;                // the shortest pattern a term names
+    // The links' upper bounds (within), one word per record and in the records'
+    // order, PM_SQ_FREE where a term has none; empty where no term of the set
+    // has one.  They travel beside the records: the 3-word record stays.
+    std::vector<uint32_t> wins;
+    uint32_t within_run = 0;  // the longest run of consecutive bounded links in any rule
 };
 
 // 0, or -2 for what pm_flat_seq_rule_tables rejects (img is then unspecified).
 int pm_seq_rules_image(const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps, size_t nrules,
                        const uint32_t* pattern_len, size_t npat, PmSeqRulesImage& img);
+// The same with withins parallel to gaps (NULL: every one PM_SQ_FREE), checked as
+// pm_flat_seq_rule_tables_within checks them.
+int pm_seq_rules_image_within(const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
+                              const uint32_t* withins, size_t nrules, const uint32_t* pattern_len, size_t npat,
+                              PmSeqRulesImage& img);
 
 // The device tables of one object.
 struct PmSeqRulesDev {
@@ -98,6 +108,8 @@ struct PmSeqRulesDev {
     uint32_t ngid = 0;    // npat + 1: a gid at or above it anchors nothing
     uint32_t nrules = 0;
     uint32_t nterms = 0;  // the records of recs
+    const uint32_t* wins = nullptr;  // nterms words, NULL where the set has no bound
+    uint32_t within_run = 0;         // > 0: the walk with an upper bound (sq_eval_within_kernel) evaluates the set
 };
 
 #ifdef __HIPCC__

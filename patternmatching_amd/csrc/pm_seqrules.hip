@@ -8,6 +8,9 @@
 //   pm_bystream.hip) -> scatter of the positions -> sort of the short ranges,
 //   work list of the long ones -> sort of the long ranges -> evaluate + count
 //   -> scan over the streams (3 launches) -> evaluate + scatter
+// A set with an upper bound on some link (within) is evaluated by
+// sq_eval_within_kernel, pm_seqwalk.h's exact walk, in sq_eval_kernel's place;
+// everything before the evaluation is shared.
 // After the insert the table's keys are frozen, after the sorts the positions:
 // both evaluations read them with plain loads and so find the same hits.  The
 // number of events used, min(*nevents, cap), is read on the device, and so is
@@ -24,6 +27,7 @@
 
 #include "pm_bystream_dev.h"
 #include "pm_seqrules.h"
+#include "pm_seqwalk.h"
 
 namespace {
 
@@ -366,6 +370,107 @@ sq_eval_kernel(const u64* __restrict__ keys, const u64* __restrict__ pos, const 
     }
 }
 
+// What pm_seqwalk.h's walk reads on the device: the frozen table, the sorted
+// positions and the set's records and bounds.  A record index is clamped below
+// nterms; a range is sq_range's, inside [0, cap].
+struct SqWalkDev {
+    const u64* __restrict__ keys;
+    const int64_t* __restrict__ start;
+    const u64* __restrict__ occ_;
+    const uint32_t* __restrict__ recs;
+    const uint32_t* __restrict__ wins;
+    uint64_t table, cap;
+    u64 skey;
+    int shift;
+    uint32_t nterms;
+    __device__ __forceinline__ size_t at(uint32_t q) const { return q < nterms ? q : nterms - 1; }
+    __device__ __forceinline__ uint32_t term(uint32_t q) const { return recs[at(q) * PM_SQ_REC]; }
+    __device__ __forceinline__ uint32_t gap(uint32_t q) const { return recs[at(q) * PM_SQ_REC + 1]; }
+    __device__ __forceinline__ uint32_t len(uint32_t q) const { return recs[at(q) * PM_SQ_REC + 2]; }
+    __device__ __forceinline__ uint32_t within(uint32_t q) const { return wins[at(q)]; }
+    __device__ __forceinline__ bool range(uint32_t q, uint64_t& a, uint64_t& b) const {
+        uint64_t h = 0;
+        if (!sq_probe(keys, skey | (term(q) & PM_BS_GID_MASK), table - 1, shift, table, h)) return false;
+        sq_range(start, h, cap, a, b);
+        return true;
+    }
+    __device__ __forceinline__ uint64_t occ(uint64_t i) const { return occ_[i]; }
+};
+
+// Passes 5 and 7 of a set with at least one bounded link: sq_eval_kernel's
+// structure with pm_seqwalk.h's walk inside a rule.  The cursors of a lane's
+// run lie in dynamic LDS as u32, [level][thread]: a lane's bank is its lane
+// number whatever level it is on, so lanes on different levels never
+// conflict.  max_run levels (BS_THREADS x 4 x max_run bytes) come with the
+// launch; a run longer than that does not fire (the host sized it: none is).
+// max_turns bounds the walk's loop.
+template <bool SCATTER>
+__global__ void __launch_bounds__(BS_THREADS)
+sq_eval_within_kernel(const u64* __restrict__ keys, const int64_t* __restrict__ start, const u64* __restrict__ occ,
+                      uint64_t table, uint64_t cap, int shift, int64_t nseg, const uint32_t* __restrict__ anchor_ptr,
+                      const uint32_t* __restrict__ anchor_rules, const uint32_t* __restrict__ rterm_ptr,
+                      const uint32_t* __restrict__ recs, const uint32_t* __restrict__ wins, uint32_t ngid,
+                      uint32_t nrules, uint32_t nterms, uint32_t max_run, uint64_t max_turns, u64* __restrict__ cnt,
+                      const int64_t* __restrict__ rule_ptr, uint64_t* __restrict__ hits, uint64_t hits_cap) {
+    extern __shared__ uint32_t sq_cursors[];
+    const uint64_t stride = (uint64_t)gridDim.x * BS_THREADS;
+    const int lane = threadIdx.x & 63;
+    for (uint64_t i = (uint64_t)blockIdx.x * BS_THREADS + threadIdx.x; i < table; i += stride) {
+        const u64 k = keys[i];
+        const u64 kj = k >> PM_BS_GID_BITS;
+        const uint32_t g = (uint32_t)(k & PM_BS_GID_MASK);
+        uint32_t a0 = 0, a1 = 0;
+        if (k != BS_EMPTY && kj < (u64)nseg && g < ngid) {
+            a1 = anchor_ptr[g + 1];
+            a1 = a1 < nrules ? a1 : nrules;
+            a0 = anchor_ptr[g];
+            a0 = a0 < a1 ? a0 : a1;
+        }
+        uint64_t pending = __ballot(a1 > a0);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            pending &= pending - 1;
+            const uint32_t lj = (uint32_t)__shfl((int)(uint32_t)kj, leader);  // < nseg < 2^31
+            const uint32_t lbeg = (uint32_t)__shfl((int)a0, leader), lend = (uint32_t)__shfl((int)a1, leader);
+            const SqWalkDev tables{keys, start, occ, recs, wins, table, cap, (u64)lj << PM_BS_GID_BITS, shift, nterms};
+            u64 slot_hits = 0;
+            for (uint32_t base = lbeg; base < lend; base += 64) {  // lend - lbeg <= nrules
+                const uint32_t idx = base + (uint32_t)lane;
+                bool fires = false;
+                uint64_t hp = 0;
+                uint32_t r = 0;
+                if (idx < lend) {
+                    r = anchor_rules[idx];
+                    if (r < nrules && nterms) {
+                        uint32_t t1 = rterm_ptr[r + 1];
+                        t1 = t1 < nterms ? t1 : nterms;
+                        uint32_t t0 = rterm_ptr[r];
+                        t0 = t0 < t1 ? t0 : t1;
+                        if (t1 - t0 > PM_RL_MAX_TERMS) t1 = t0 + PM_RL_MAX_TERMS;
+                        fires = t1 > t0 &&
+                                pm_sw_rule(tables, t0, t1, sq_cursors + threadIdx.x, BS_THREADS, max_run, max_turns, hp);
+                    }
+                }
+                const uint64_t fired = __ballot(fires);
+                if (!fired) continue;
+                const u64 n = (u64)__popcll(fired);
+                if (SCATTER) {
+                    u64 at = 0;
+                    if (lane == 0) at = atomicAdd(&cnt[lj], (u64)0 - n) - n;
+                    at = (u64)__shfl((long long)at, 0);
+                    if (fires) {
+                        const uint64_t slot = (uint64_t)rule_ptr[lj] + at + (u64)__popcll(fired & ((1ull << lane) - 1));
+                        if (slot < hits_cap) hits[slot] = ((u64)hp << PM_BS_GID_BITS) | r;
+                    }
+                } else {
+                    slot_hits += n;
+                }
+            }
+            if (!SCATTER && slot_hits && lane == 0) atomicAdd(&cnt[lj], slot_hits);
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t pm_launch_seq_rules_by_stream(const uint64_t* events, uint64_t cap, const unsigned long long* nevents,
@@ -405,6 +510,24 @@ hipError_t pm_launch_seq_rules_by_stream(const uint64_t* events, uint64_t cap, c
     // the work list is seldom long: a grid of its capacity, at most one grid of the device
     sq_sort_long_kernel<<<pm_bs_grid(l.wl_cap * BS_THREADS, num_cu), BS_THREADS, 0, s>>>(start, occ, l.table, cap, wl,
                                                                                          wlcur, l.wl_cap);
+    if (rules.within_run) {
+        // a set with a bound: the exact walk, one u32 cursor per level of a run and thread in LDS.  A turn of
+        // the walk moves a cursor forward, touches a level for the first time or follows from such a turn: at
+        // most 64 ranges of at most cap positions
+        const uint32_t run = rules.within_run < PM_RL_MAX_TERMS ? rules.within_run : PM_RL_MAX_TERMS - 1;
+        const size_t lds = (size_t)BS_THREADS * sizeof(uint32_t) * run;
+        const uint64_t max_turns = 4 * (uint64_t)PM_RL_MAX_TERMS * (cap + 2);
+        sq_eval_within_kernel<false><<<tgrid, BS_THREADS, lds, s>>>(
+            keys, start, occ, l.table, cap, shift, nseg, rules.anchor_ptr, rules.anchor_rules, rules.rterm_ptr,
+            rules.recs, rules.wins, rules.ngid, rules.nrules, rules.nterms, run, max_turns, cnt, rule_ptr, hits,
+            hits_cap);
+        pm_launch_bs_scan(cnt, nseg, bsum, rule_ptr, s);
+        sq_eval_within_kernel<true><<<tgrid, BS_THREADS, lds, s>>>(
+            keys, start, occ, l.table, cap, shift, nseg, rules.anchor_ptr, rules.anchor_rules, rules.rterm_ptr,
+            rules.recs, rules.wins, rules.ngid, rules.nrules, rules.nterms, run, max_turns, cnt, rule_ptr, hits,
+            hits_cap);
+        return hipGetLastError();
+    }
     sq_eval_kernel<false><<<tgrid, BS_THREADS, 0, s>>>(keys, pos, start, occ, l.table, cap, shift, nseg,
                                                         rules.anchor_ptr, rules.anchor_rules, rules.rterm_ptr,
                                                         rules.recs, rules.ngid, rules.nrules, rules.nterms, cnt,

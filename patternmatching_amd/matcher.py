@@ -241,62 +241,104 @@ def rules_by_stream_host(events, offsets, rules, hits_cap=None):
 SEQ_FREE = 0xFFFFFFFF  # PM_SEQ_FREE: the term may lie anywhere in the stream
 
 
-def pack_seq_rules(rules, fast=None):
-    """(term_ptr u32 of len(rules) + 1, terms u32, gaps u32): the form that
-    pm_hip_set_seq_rules takes.  A rule is a sequence of (gid, gap) pairs: g
-    a positive term, -g a negated one; gap None for a free term (PM_SEQ_FREE),
-    or d >= 0: the term begins at least d bytes after the positive term listed
-    before it has ended.  fast[r] is the gid of rule r's RULE_FAST term (the
-    first positive term of that gid), or None."""
+def _pack_seq(rules, fast):
+    """(term_ptr, terms, gaps, withins, whether any term has a within)."""
     rules = [[tuple(t) for t in r] for r in rules]
     if fast is not None and len(fast) != len(rules):
         raise ValueError("fast: one gid or None per rule")
     ptr = np.zeros(len(rules) + 1, dtype=np.uint32)
-    terms, gaps = [], []
+    terms, gaps, withins = [], [], []
+    bounded = False
     for r, rule in enumerate(rules):
         f = None if fast is None else fast[r]
-        if f is not None and f not in [g for g, _ in rule]:
+        if f is not None and f not in [t[0] for t in rule]:
             raise ValueError(f"fast[{r}] = {f} is no positive term of rule {r}")
-        for g, gap in rule:
-            g = int(g)
+        for term in rule:
+            if len(term) not in (2, 3):
+                raise ValueError(f"rule {r}: a term is (gid, gap) or (gid, gap, within), not {term}")
+            g, gap, within = int(term[0]), term[1], (term[2] if len(term) == 3 else None)
             if g == 0 or abs(g) >= 1 << EVENT_GID_BITS:
                 raise ValueError(f"rule {r}: a term is a gid in [1, 2^24) or its negative, not {g}")
             if gap is not None and not 0 <= int(gap) <= 0x7FFFFFFF:
                 raise ValueError(f"rule {r}: a gap is None or a distance in [0, 2^31), not {gap}")
+            if within is not None:
+                if not 0 <= int(within) <= 0x7FFFFFFF:
+                    raise ValueError(f"rule {r}: a within is None or a bound in [0, 2^31), not {within}")
+                bounded = True
+                gap = 0 if gap is None else gap  # Snort's bare within
             if g == f:
                 terms.append(g | RULE_FAST)
                 f = None
             else:
                 terms.append((-g | RULE_NEGATED) if g < 0 else g)
             gaps.append(SEQ_FREE if gap is None else int(gap))
+            withins.append(SEQ_FREE if within is None else int(within))
         ptr[r + 1] = len(terms)
-    return ptr, np.asarray(terms, dtype=np.uint32), np.asarray(gaps, dtype=np.uint32)
+    u32 = lambda v: np.asarray(v, dtype=np.uint32)  # noqa: E731
+    return ptr, u32(terms), u32(gaps), u32(withins), bounded
+
+
+def pack_seq_rules(rules, fast=None):
+    """(term_ptr u32 of len(rules) + 1, terms u32, gaps u32): the form that
+    pm_hip_set_seq_rules takes.  A rule is a sequence of (gid, gap) pairs: g
+    a positive term, -g a negated one; gap None for a free term (PM_SEQ_FREE),
+    or d >= 0: the term begins at least d bytes after the positive term listed
+    before it has ended.  fast[r] is the gid of rule r's RULE_FAST term (the
+    first positive term of that gid), or None.  A term that carries a within
+    is an error here: pack_seq_rules_within packs those."""
+    ptr, terms, gaps, _, bounded = _pack_seq(rules, fast)
+    if bounded:
+        raise ValueError("a term carries a within: pack_seq_rules_within packs such rules")
+    return ptr, terms, gaps
+
+
+def pack_seq_rules_within(rules, fast=None):
+    """(term_ptr, terms, gaps, withins), the form that
+    pm_hip_set_seq_rules_within takes: pack_seq_rules' rules, in which a term
+    may also be (gid, gap, within): within None for no upper bound
+    (PM_SEQ_FREE), or w >= 0: the term ends at most w bytes after the positive
+    term listed before it has ended.  A within with gap None means gap 0
+    (Snort's bare within)."""
+    return _pack_seq(rules, fast)[:4]
+
+
+def _packed_seq(rules, fast=None):
+    """(term_ptr, terms, gaps, withins or None) of rules in either packed form
+    (a tuple of 3 or 4 arrays) or as any sequence of rules; withins None where
+    no term has a bound."""
+    if isinstance(rules, tuple) and len(rules) in (3, 4) and all(isinstance(a, np.ndarray) for a in rules):
+        return tuple(rules) + (None,) if len(rules) == 3 else tuple(rules)
+    ptr, terms, gaps, withins, bounded = _pack_seq(rules, fast)
+    return ptr, terms, gaps, withins if bounded else None
 
 
 def seq_rules_by_stream_host(events, offsets, rules, pattern_len, hits_cap=None):
     """pm_flat_seq_rules_by_stream, the host twin of
     HipMatcher.seq_rules_by_stream (no matcher, no device): (rule_ptr int64 of
     nseg + 1, hits u64 of position << 24 | rule) with each stream's range
-    ascending; rules as pack_seq_rules takes them, or its (term_ptr, terms,
-    gaps) triple; pattern_len the patterns' lengths by gid ([0] == 0), which
-    the links need."""
+    ascending; rules as pack_seq_rules or pack_seq_rules_within takes them, or
+    the packed triple or 4-tuple; pattern_len the patterns' lengths by gid
+    ([0] == 0), which the links need.  Rules with a within go through
+    pm_flat_seq_rules_by_stream_within."""
     ev = np.ascontiguousarray(events, dtype=np.uint64).ravel()
     offs = np.ascontiguousarray(offsets, dtype=np.int64)
     if offs.ndim != 1 or offs.size < 1:
         raise ValueError("offsets: nseg + 1 values")
-    tptr, terms, gaps = rules if isinstance(rules, tuple) else pack_seq_rules(rules)
+    tptr, terms, gaps, withins = _packed_seq(rules)
     plen = np.ascontiguousarray(pattern_len, dtype=np.uint32)
     u64p, i64p, u32p = (ctypes.POINTER(t) for t in (ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32))
     ptr = np.zeros(offs.size, dtype=np.int64)
     hits = np.empty(0 if hits_cap is None else hits_cap, dtype=np.uint64)
+    head = (ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p), offs.size - 1, tptr.ctypes.data_as(u32p),
+            terms.ctypes.data_as(u32p), gaps.ctypes.data_as(u32p))
+    name = "pm_flat_seq_rules_by_stream" if withins is None else "pm_flat_seq_rules_by_stream_within"
+    if withins is not None:
+        head += (withins.ctypes.data_as(u32p),)
     for _ in range(2):  # the hits are not bounded by the events: the first call counts them
-        rc = load().pm_flat_seq_rules_by_stream(ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p),
-                                                offs.size - 1, tptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
-                                                gaps.ctypes.data_as(u32p), len(tptr) - 1, plen.ctypes.data_as(u32p),
-                                                len(plen) - 1, hits.ctypes.data_as(u64p), len(hits),
-                                                ptr.ctypes.data_as(i64p))
+        rc = getattr(load(), name)(*head, len(tptr) - 1, plen.ctypes.data_as(u32p), len(plen) - 1,
+                                   hits.ctypes.data_as(u64p), len(hits), ptr.ctypes.data_as(i64p))
         if rc != 0:
-            raise ValueError(f"pm_flat_seq_rules_by_stream: bad arguments ({rc})")
+            raise ValueError(f"{name}: bad arguments ({rc})")
         if hits_cap is not None or len(hits) >= ptr[-1]:
             break
         hits = np.empty(int(ptr[-1]), dtype=np.uint64)
@@ -1027,12 +1069,27 @@ class HipMatcher:
         (gid, gap) pairs as pack_seq_rules takes them: gap None for a free
         term, d >= 0 for one that begins at least d bytes after the positive
         term before it has ended (d = 0 is Snort's distance:0); -gid a negated
-        term.  After compile(); a later call replaces the rules (no
+        term.  A term may also be (gid, gap, within) as pack_seq_rules_within
+        takes it: it ends at most within bytes after the term before it has
+        ended (pm_hip_set_seq_rules_within; any such term and the exact walk
+        evaluates the set).  After compile(); a later call replaces the rules (no
         ordered-rules call may be in flight)."""
-        ptr, terms, gaps = pack_seq_rules(rules, fast)
+        ptr, terms, gaps, withins = _packed_seq(rules, fast)
         u32p = ctypes.POINTER(ctypes.c_uint32)
-        self._check(self.lib.pm_hip_set_seq_rules(self.obj, ptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
-                                                  gaps.ctypes.data_as(u32p), len(ptr) - 1))
+        if withins is None:
+            rc = self.lib.pm_hip_set_seq_rules(self.obj, ptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
+                                               gaps.ctypes.data_as(u32p), len(ptr) - 1)
+        else:
+            rc = self.lib.pm_hip_set_seq_rules_within(self.obj, ptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
+                                                      gaps.ctypes.data_as(u32p), withins.ctypes.data_as(u32p),
+                                                      len(ptr) - 1)
+        self._check(rc)
+
+    def seq_rules_within_run(self):
+        """pm_hip_seq_rules_within_run: the longest run of consecutive bounded
+        links (terms with a within) in any rule of the set; 0 where no term
+        has a bound and before set_seq_rules."""
+        return int(self.lib.pm_hip_seq_rules_within_run(self.obj))
 
     def seq_rule_count(self):
         """pm_hip_seq_rule_count: the ordered rules set (0 before set_seq_rules)."""
