@@ -943,9 +943,9 @@ int pm_flat_flow_rules(const uint64_t* events, size_t nevents, const int64_t* of
  * one (the proof is in DESIGN.md §4, "Ordered rules").
  * The list has the rules call's preconditions: an all-matches form, at a
  * min_len <= pm_hip_seq_rules_min_len, with a cap that held the list.
- * Out of scope: negative distances, relative negated terms, and flows: like
- * the rules call this one knows no flows and carries no chain from one packet
- * to the next.
+ * Out of scope: negative distances and relative negated terms.  This call
+ * knows no flows; the flow ordered rules below (pm_hip_flow_seq_rules_device)
+ * carry each chain's progress from one packet of a flow to the next.
  * Within: an upper bound on a link.  Beside gaps[] a rule set may carry a
  * second parallel uint32_t withins[], one value per term:
  *   - PM_SEQ_FREE: no upper bound; the term is as above;
@@ -1095,6 +1095,140 @@ int pm_flat_seq_rules_by_stream(const uint64_t* events, size_t nevents, const in
                                 const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps, size_t nrules,
                                 const uint32_t* pattern_len, size_t npat, uint64_t* hits, size_t hits_cap,
                                 int64_t* rule_ptr);
+
+/*
+ * Flow ordered rules: ordered rules (distance only) whose terms lie in
+ * different packets of one flow -- content:"A"; content:"B"; distance:N; with
+ * A and B in different TCP segments.  The caller keeps one progress row per
+ * live flow ON THE DEVICE, and one call, behind any flow list scan, reports
+ * the ordered rules that became true in this call's bytes and advances the
+ * rows.
+ * Rule set.  pm_hip_set_flow_seq_rules(obj, term_ptr, terms, gaps, nrules)
+ * takes a rule set of its own, independent of pm_hip_set_rules,
+ * pm_hip_set_flow_rules and pm_hip_set_seq_rules: an object may hold any of
+ * the four.  It runs every check of pm_hip_set_seq_rules with the same return
+ * codes (-1 before compile(); -2 with one message; nothing changes on an
+ * error).  withins are not accepted: a bound across packets needs a carried
+ * feasible set per level and is out of scope, as are negative distances and
+ * relative negated terms.  PM_RULE_FAST is accepted and has no effect on the
+ * results.  The device tables (the bit of each gid; an inverted index from
+ * every DISTINCT positive gid of a rule to the rule; the ordered rules'
+ * records; each rule's first chain word) live in allocations of their own,
+ * counted in pm_hip_table_bytes, replaced by a later call after a device
+ * synchronize and freed with the object.
+ * pm_hip_flow_seq_rule_count: the rules set (0 before).
+ * pm_hip_flow_seq_rules_min_len: the shortest pattern any term names (0 before).
+ * Row layout.  A row has S = max(1, C + W) u64 words (pm_hip_flow_seq_rule_words;
+ * 0 before).
+ *   Chain words.  The chains with at least two positive terms are numbered c =
+ *   0 .. C - 1, by rule and then by the head's place in the rule
+ *   (pm_hip_flow_seq_chain_count = C).  Word c is 0 while the chain's head has
+ *   not been seen in the flow; else (E + 1) << 6 | k, where k in 0..63 is the
+ *   deepest level chosen so far (0: the head) and E the flow byte index at
+ *   which that level's chosen occurrence ends.  A chain is done when k is its
+ *   last level.  pm_hip_flow_seq_chain_word(obj, rule, term_index): the word
+ *   of the chain headed by that term of that rule, as the rule was given, or -1.
+ *   Bits.  K is the number of distinct gids named by a chain of one term or by
+ *   a negated term; a gid's bit is its rank among them, ascending
+ *   (pm_hip_flow_seq_rule_bit(obj, gid), or -1).  Bit b lives in word C + b /
+ *   64 at bit b % 64 and says that the gid has occurred in the flow.  W =
+ *   ceil(K / 64).
+ * A zeroed row is a fresh flow.  pm_flat_flow_seq_rule_layout gives the same
+ * layout on the host alone (chain_word_out: one value per term, 0xFFFFFFFF
+ * where the term heads no such chain; bit_by_gid_out[npat + 1], 0xFFFFFFFF: no
+ * bit; C, K and S), so the host twin's rows and the device's are bit-identical.
+ * Semantics.  For one flow let P_k be the flow's bytes through call k, taken
+ * as one stream, its events re-based to flow positions.  The hits of call k
+ * are exactly the hits of pm_hip_seq_rules_by_stream_device (distance only)
+ * over P_k whose position lies in call k's bytes, reported as position << 24 |
+ * rule with the position buffer-global, in the events' own format.  So:
+ *   - a rule fires at most once per flow;
+ *   - a negated term seen in an earlier call, or anywhere in this call (even
+ *     after the completing byte), suppresses the rule;
+ *   - a negated term that first appears in a later call retracts nothing.  So
+ *     the union of a flow's hits over its calls equals the ordered-rules call's
+ *     hits over the uncut flow for every rule without a negated term, whatever
+ *     the cuts; for a rule with one, the uncut flow's hits are a subset of the
+ *     union: a cut may report a rule that a negation further on would have
+ *     suppressed in the flow as a whole;
+ *   - a link is measured in flow bytes: a follower in packet 3 may follow a
+ *     head in packet 1, and an occurrence that straddles a cut counts with its
+ *     true start (a follower that begins before its head has ended does not
+ *     satisfy the link, wherever the cut lies).
+ * Greedy stays exact across calls: a level's chosen position depends only on
+ * the occurrences at or below it and later calls only add larger positions, so
+ * a level once chosen never changes ("Flow ordered rules").  A
+ * rule fires in a call iff every chain is done, at least one of them reached
+ * its last level in this call, and no negated gid is carried or held; the
+ * hit's position is the largest completing position of this call.
+ * pm_hip_flow_seq_rules_device(obj, d_events, cap, d_nevents, d_offsets, nseg,
+ * d_prog, nrows, d_rows, d_pos_in, flags, d_hits, hits_cap, d_rule_ptr,
+ * d_scratch, scratch_bytes, hip_stream): the list, the hits, d_rule_ptr,
+ * d_rows, nrows, the inert rows and PM_FLOW_RULES_KEEP are exactly those of
+ * pm_hip_flow_rules_device, with d_prog (nrows x S u64) in the place of d_sets.
+ * d_pos_in is nseg u64, the bytes each flow had before this call, as the
+ * window scan takes them; it is required.  A stream with pos_in + length above
+ * 2^57 is inert.  Without PM_FLOW_RULES_KEEP the rows are advanced whatever
+ * hits_cap is: every chain of a rule with a positive term in this call's bytes
+ * is advanced as far as this call's occurrences take it, fired or not, and
+ * every gid with a bit that occurs gets its bit.  After a commit the same call
+ * reports nothing.  One row named by two streams of one call gives unspecified
+ * rows and hits for them, never an access outside the arrays.
+ * Scratch: pm_hip_flow_seq_rules_scratch_bytes(cap, nseg), the ordered-rules
+ * call's formula.  Like its siblings the call allocates nothing, never waits
+ * for the host, may be captured in a graph, reads the list's cursor on the
+ * device and asks the resident read_block server to leave the device first.
+ * Returns 0; -1 before compile(); -2 bad arguments: the flow-rules call's
+ * cases with d_prog and S for d_sets and W, and d_pos_in NULL or misaligned;
+ * -12 pm_hip_set_flow_seq_rules was not called; -3 launch error.  Nothing is
+ * launched or written when a check fails.  nseg == 0: returns 0 and launches
+ * nothing.  cap == 0 with nseg > 0: an all-zero d_rule_ptr and untouched rows.
+ * Memory safety does not depend on the data: beyond the ordered-rules call's
+ * clamps a row index is tested against nrows wherever it is read, a chain-word
+ * index against C and S, a bit's word against S, an index range against the
+ * index array and a level against its chain's last.
+ * pm_hip_flow_seq_rules: the host form, as pm_hip_flow_rules: host arrays
+ * (prog updated in place, pos_in nseg u64) staged on the object's batch
+ * stream; the committing call runs exactly once, behind a PM_FLOW_RULES_KEEP
+ * call where its hits staging may be short; each range sorted ascending.
+ * pm_flat_flow_seq_rules: the twin of the device call over host arrays, the
+ * rows updated in place, each range sorted ascending; it has an index of its
+ * own and does not use the device's walk; words must be the set's S; 0, or -2
+ * for what the device call rejects (and a wrong words), with nothing written.
+ * Measured (snort, 64 MiB in 44,740 packets of 1,500 bytes, one per flow and
+ * call, two calls behind the flow scan at min_len 3, 1,000 synthetic ordered
+ * rules, S = 1,020; profiles/flowseqrules/): the call alone takes 0.13-0.15 ms
+ * on random ASCII (51 thousand events) and 8.2-8.3 ms on the lines stream (14.6
+ * million events), 1.3-1.6x and 1.5x the ordered-rules call on the same list,
+ * and 0.0074-0.019x / 0.0051-0.0054x of the list copied to the host and walked
+ * by pm_flat_flow_seq_rules on one thread ("Flow ordered rules").
+ */
+int pm_hip_set_flow_seq_rules(void* obj, const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
+                              size_t nrules);
+size_t pm_hip_flow_seq_rule_count(void* obj);
+uint32_t pm_hip_flow_seq_rules_min_len(void* obj);
+uint32_t pm_hip_flow_seq_rule_words(void* obj);
+uint32_t pm_hip_flow_seq_chain_count(void* obj);
+int64_t pm_hip_flow_seq_chain_word(void* obj, size_t rule, uint32_t term_index);
+int64_t pm_hip_flow_seq_rule_bit(void* obj, uint32_t gid);
+size_t pm_hip_flow_seq_rules_scratch_bytes(uint64_t cap, int64_t nseg);
+int pm_hip_flow_seq_rules_device(void* obj, const uint64_t* d_events, uint64_t cap, const unsigned long long* d_nevents,
+                                 const int64_t* d_offsets, int64_t nseg, uint64_t* d_prog, int64_t nrows,
+                                 const int64_t* d_rows, const uint64_t* d_pos_in, uint32_t flags, uint64_t* d_hits,
+                                 uint64_t hits_cap, int64_t* d_rule_ptr, void* d_scratch, size_t scratch_bytes,
+                                 void* hip_stream);
+int pm_hip_flow_seq_rules(void* obj, const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                          uint64_t* prog, size_t nrows, const int64_t* rows, const uint64_t* pos_in, uint32_t flags,
+                          uint64_t* hits, size_t hits_cap, int64_t* rule_ptr);
+int pm_flat_flow_seq_rule_layout(const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps, size_t nrules,
+                                 const uint32_t* pattern_len, size_t npat, uint32_t* chain_word_out,
+                                 uint32_t* bit_by_gid_out, uint32_t* nchains_out, uint32_t* nbits_out,
+                                 uint32_t* words_out);
+int pm_flat_flow_seq_rules(const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                           const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps, size_t nrules,
+                           const uint32_t* pattern_len, size_t npat, uint64_t* prog, size_t nrows, size_t words,
+                           const int64_t* rows, const uint64_t* pos_in, uint32_t flags, uint64_t* hits,
+                           size_t hits_cap, int64_t* rule_ptr);
 
 /* Accuracy of one dense u32 gid stream against a reference one, on the
  * device (the scoring of Core/src/measure.c:174-190 with is_pattern_suffix,

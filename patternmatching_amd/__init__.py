@@ -49,6 +49,12 @@ interface:
                     without a device (the host twin of
                     HipMatcher.set_seq_rules / seq_rules_by_stream /
                     seq_rules_by_stream_device / read_many_seq_rules)
+    flow_seq_rules_host     ordered rules (distance only) whose terms lie in
+                    different packets of a flow: a progress row per flow, the
+                    rules that become true in each call, without a device (the
+                    host twin of HipMatcher.set_flow_seq_rules / flow_seq_rules
+                    / flow_seq_rules_device and FlowTable.scan_seq_rules;
+                    flow_seq_rule_layout_host gives the rows' layout)
 """
 from ._lib import load, LIB_PATH, CLI_PATH  # noqa: F401
 from .matcher import (  # noqa: F401
@@ -67,6 +73,8 @@ from .matcher import (  # noqa: F401
     pack_seq_rules,
     pack_seq_rules_within,
     seq_rules_by_stream_host,
+    flow_seq_rules_host,
+    flow_seq_rule_layout_host,
     SEQ_FREE,
     FLOW_RULES_KEEP,
     RULE_NEGATED,
@@ -80,5 +88,5 @@ from .matcher import (  # noqa: F401
 __all__ = ["load", "Dictionary", "HipMatcher", "FlowTable", "gen_stream", "batch_offsets", "unpack_events", "parse_line",
            "events_by_stream_host", "BY_STREAM_UNIQUE", "pack_rules", "rules_by_stream_host",
            "flow_rules_host", "flow_rule_bits_host", "pack_seq_rules", "pack_seq_rules_within",
-           "seq_rules_by_stream_host", "SEQ_FREE", "FLOW_RULES_KEEP", "RULE_NEGATED", "RULE_FAST", "KIND_RT", "KIND_AC",
-           "KIND_AUTO", "LIB_PATH", "CLI_PATH"]
+           "seq_rules_by_stream_host", "flow_seq_rules_host", "flow_seq_rule_layout_host", "SEQ_FREE",
+           "FLOW_RULES_KEEP", "RULE_NEGATED", "RULE_FAST", "KIND_RT", "KIND_AC", "KIND_AUTO", "LIB_PATH", "CLI_PATH"]

@@ -322,6 +322,32 @@ SIGNATURES = {
                                                    c_u32p, ctypes.c_size_t, c_u32p, ctypes.c_size_t,
                                                    ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
                                                    ctypes.POINTER(ctypes.c_int64)]),
+    "pm_hip_set_flow_seq_rules": (ctypes.c_int, [c_vp, c_u32p, c_u32p, c_u32p, ctypes.c_size_t]),
+    "pm_hip_flow_seq_rule_count": (ctypes.c_size_t, [c_vp]),
+    "pm_hip_flow_seq_rules_min_len": (ctypes.c_uint32, [c_vp]),
+    "pm_hip_flow_seq_rule_words": (ctypes.c_uint32, [c_vp]),
+    "pm_hip_flow_seq_chain_count": (ctypes.c_uint32, [c_vp]),
+    "pm_hip_flow_seq_chain_word": (ctypes.c_int64, [c_vp, ctypes.c_size_t, ctypes.c_uint32]),
+    "pm_hip_flow_seq_rule_bit": (ctypes.c_int64, [c_vp, ctypes.c_uint32]),
+    "pm_hip_flow_seq_rules_scratch_bytes": (ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_int64]),
+    "pm_hip_flow_seq_rules_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_uint64, c_vp, c_vp, ctypes.c_int64, c_vp,
+                                                    ctypes.c_int64, c_vp, c_vp, ctypes.c_uint32, c_vp, ctypes.c_uint64,
+                                                    c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "pm_hip_flow_seq_rules": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64),
+                                             ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_int64)]),
+    "pm_flat_flow_seq_rule_layout": (ctypes.c_int, [c_u32p, c_u32p, c_u32p, ctypes.c_size_t, c_u32p, ctypes.c_size_t,
+                                                    c_u32p, c_u32p, c_u32p, c_u32p, c_u32p]),
+    "pm_flat_flow_seq_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+                                              ctypes.POINTER(ctypes.c_int64), ctypes.c_size_t, c_u32p, c_u32p, c_u32p,
+                                              ctypes.c_size_t, c_u32p, ctypes.c_size_t,
+                                              ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, ctypes.c_size_t,
+                                              ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64),
+                                              ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+                                              ctypes.POINTER(ctypes.c_int64)]),
 }
 
 _lib = None

@@ -39,6 +39,7 @@
 #include "pm_hoststep.h"
 #include "pm_kernels.h"
 #include "pm_flowrules.h"
+#include "pm_flowseqrules.h"
 #include "pm_rules.h"
 #include "pm_seqrules.h"
 #include "pm_streamgen.h"
@@ -351,6 +352,15 @@ struct PmHip {
     uint32_t seq_rules_min_len = 0;
     std::vector<void*> seq_rules_allocs;
     size_t seq_rules_bytes = 0;
+    // flow ordered rules (pm_hip_set_flow_seq_rules): a rule set of their own, held the same way
+    PmFlowSeqRulesDev flow_seq_rules{};
+    uint32_t flow_seq_rules_min_len = 0;
+    uint32_t flow_seq_rules_fanout = 0;  // the most rules one gid indexes (bounds the host form's hits)
+    std::vector<uint32_t> flow_seq_rule_bits;   // host copy of gid_bit (pm_hip_flow_seq_rule_bit)
+    std::vector<uint32_t> flow_seq_chain_words;  // by term, as given (pm_hip_flow_seq_chain_word)
+    std::vector<uint32_t> flow_seq_term_ptr;     // the set's term_ptr
+    std::vector<void*> flow_seq_rules_allocs;
+    size_t flow_seq_rules_bytes = 0;
     std::string cache_dir;  // compiled-image cache (else $PM_IMAGE_CACHE)
     bool cache_hit = false;
     std::vector<void*> allocs;
@@ -1448,6 +1458,7 @@ void pm_hip_free(void* obj) {
     for (void* p : o->rules_allocs) (void)hipFree(p);
     for (void* p : o->flow_rules_allocs) (void)hipFree(p);
     for (void* p : o->seq_rules_allocs) (void)hipFree(p);
+    for (void* p : o->flow_seq_rules_allocs) (void)hipFree(p);
     if (o->spill) (void)hipFree(o->spill);
     for (StreamSpill& x : o->sspill) {
         if (x.buf) (void)hipFree(x.buf);
@@ -3126,6 +3137,229 @@ int pm_hip_seq_rules_by_stream(void* obj, const uint64_t* events, size_t nevents
     const size_t total = (size_t)ptr[nseg];
     std::vector<uint64_t> hv(total);
     if (total) PM_CHECK(hipMemcpyAsync(hv.data(), q.d_rl_hits, total * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    PM_CHECK(hipStreamSynchronize(q.s));
+    par_range(nseg, (size_t)1 << 12, [&](size_t lo, size_t hi) {
+        for (size_t j = lo; j < hi; ++j) std::sort(hv.begin() + ptr[j], hv.begin() + ptr[j + 1]);
+    });
+    std::memcpy(rule_ptr, ptr.data(), ptr.size() * sizeof(int64_t));
+    if (hits_cap && total) std::memcpy(hits, hv.data(), std::min(hits_cap, total) * sizeof(uint64_t));
+    return 0;
+}
+
+// ---- flow ordered rules: each chain's progress carried per flow (pm_flowseqrules.hip) ----
+// The tables of pm_flow_seq_rules_image on the device, in allocations of their
+// own, replaced like the rules' tables.  The other three rule sets and their
+// tables are not touched.
+int pm_hip_set_flow_seq_rules(void* obj, const uint32_t* term_ptr, const uint32_t* terms, const uint32_t* gaps,
+                              size_t nrules) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    PmFlowSeqRulesImage img;
+    const size_t npat = o->gids.len.empty() ? 0 : o->gids.len.size() - 1;
+    if (o->gids.len.empty() || pm_flow_seq_rules_image(term_ptr, terms, gaps, nrules, o->gids.len.data(), npat, img)) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (term_ptr, terms and gaps required, 1 <= nrules <= 2^24, term_ptr from 0, 1 to 64 "
+                      "terms per rule, a positive term in each, every gid a pattern's, no bits but the gid, "
+                      "PM_RULE_NEGATED and PM_RULE_FAST, at most one PM_RULE_FAST per rule, none on a negated term; a "
+                      "gap is PM_SEQ_FREE or at most 0x7FFFFFFF, PM_SEQ_FREE on a negated term and on the first "
+                      "positive term; a gid twice among the positive terms only as a following term, never twice "
+                      "free, never both positive and negated; no withins)");
+        return -2;
+    }
+    PM_CHECK(hipSetDevice(o->device));
+    if (!o->flow_seq_rules_allocs.empty()) {
+        PM_CHECK(hipDeviceSynchronize());  // the caller has no such call in flight; nor has this object now
+        for (void* p : o->flow_seq_rules_allocs) PM_CHECK(hipFree(p));
+        o->flow_seq_rules_allocs.clear();
+        o->table_bytes -= o->flow_seq_rules_bytes;
+        o->flow_seq_rules_bytes = 0;
+        o->flow_seq_rules = PmFlowSeqRulesDev();
+    }
+    auto up = [&](const std::vector<uint32_t>& v) {
+        void* p = nullptr;
+        const size_t bytes = v.size() * sizeof(uint32_t);
+        PM_CHECK(hipMalloc(&p, bytes));
+        PM_CHECK(hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice));
+        o->flow_seq_rules_allocs.push_back(p);
+        o->flow_seq_rules_bytes += bytes;
+        o->table_bytes += bytes;
+        return (const uint32_t*)p;
+    };
+    PmFlowSeqRulesDev d;
+    d.gid_bit = up(img.gid_bit);
+    d.idx_ptr = up(img.idx_ptr);
+    d.idx_rules = up(img.idx_rules);
+    d.rterm_ptr = up(img.rterm_ptr);
+    d.recs = up(img.recs);
+    d.rule_chain = up(img.rule_chain);
+    d.ngid = (uint32_t)(npat + 1);
+    d.nrules = (uint32_t)nrules;
+    d.nidx = (uint32_t)img.idx_rules.size();
+    d.nterms = (uint32_t)(img.recs.size() / PM_SQ_REC);
+    d.nchains = img.nchains;
+    d.words = img.words;
+    o->flow_seq_rules = d;
+    o->flow_seq_rules_min_len = img.min_len;
+    o->flow_seq_rules_fanout = img.max_fanout;
+    o->flow_seq_rule_bits = std::move(img.gid_bit);
+    o->flow_seq_chain_words = std::move(img.chain_word);
+    o->flow_seq_term_ptr.assign(term_ptr, term_ptr + nrules + 1);
+    return 0;
+}
+
+size_t pm_hip_flow_seq_rule_count(void* obj) { return as(obj)->flow_seq_rules.nrules; }
+
+uint32_t pm_hip_flow_seq_rules_min_len(void* obj) {
+    PmHip* o = as(obj);
+    return o->flow_seq_rules.nrules ? o->flow_seq_rules_min_len : 0u;
+}
+
+uint32_t pm_hip_flow_seq_rule_words(void* obj) { return as(obj)->flow_seq_rules.words; }
+
+uint32_t pm_hip_flow_seq_chain_count(void* obj) { return as(obj)->flow_seq_rules.nchains; }
+
+int64_t pm_hip_flow_seq_chain_word(void* obj, size_t rule, uint32_t term_index) {
+    PmHip* o = as(obj);
+    if (rule >= o->flow_seq_rules.nrules) return -1;
+    const uint32_t a = o->flow_seq_term_ptr[rule], b = o->flow_seq_term_ptr[rule + 1];
+    if (term_index >= b - a || o->flow_seq_chain_words[a + term_index] == PM_FS_NO_WORD) return -1;
+    return (int64_t)o->flow_seq_chain_words[a + term_index];
+}
+
+int64_t pm_hip_flow_seq_rule_bit(void* obj, uint32_t gid) {
+    PmHip* o = as(obj);
+    if (!o->flow_seq_rules.nrules || gid >= o->flow_seq_rule_bits.size() || o->flow_seq_rule_bits[gid] == PM_FR_NO_BIT)
+        return -1;
+    return (int64_t)o->flow_seq_rule_bits[gid];
+}
+
+// Every check, then the passes; nothing is written before all of them pass.
+int pm_hip_flow_seq_rules_device(void* obj, const uint64_t* d_events, uint64_t cap, const unsigned long long* d_nevents,
+                                 const int64_t* d_offsets, int64_t nseg, uint64_t* d_prog, int64_t nrows,
+                                 const int64_t* d_rows, const uint64_t* d_pos_in, uint32_t flags, uint64_t* d_hits,
+                                 uint64_t hits_cap, int64_t* d_rule_ptr, void* d_scratch, size_t scratch_bytes,
+                                 void* hip_stream) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    const uint64_t S = o->flow_seq_rules.words ? o->flow_seq_rules.words : 1;  // (before the set: -12 below)
+    bool ok = nseg >= 0 && nseg < PM_BS_MAX_NSEG && cap <= PM_BS_MAX_CAP && !misaligned(d_events, 8) &&
+              !misaligned(d_nevents, 8) && !misaligned(d_offsets, 8) && !misaligned(d_hits, 8) &&
+              !misaligned(d_rule_ptr, 8) && !misaligned(d_scratch, 16) && !misaligned(d_prog, 8) &&
+              !misaligned(d_rows, 8) && !misaligned(d_pos_in, 8) && d_pos_in && !(d_hits && d_hits == d_events) &&
+              !(cap && !d_events) && !(hits_cap && !d_hits) && !(flags & ~PM_FR_KEEP) && nrows >= 0 &&
+              (uint64_t)nrows <= PM_FR_MAX_WORDS / S && !(nrows > 0 && !d_prog) && !(!d_rows && nrows < nseg);
+    if (ok && nseg > 0)
+        ok = d_nevents && d_offsets && d_rule_ptr && d_scratch &&
+             scratch_bytes >= pm_seq_rules_layout(cap, nseg).bytes;
+    if (!ok) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (events, nevents, offsets, prog, rows, pos_in, hits and rule_ptr 8-B aligned and, "
+                      "but for rows, non-NULL, scratch non-NULL and 16-B aligned, 0 <= nseg < 2^31, cap <= 2^40, 0 <= "
+                      "nrows, nrows x words <= 2^40, nrows >= nseg without rows, no flag but PM_FLOW_RULES_KEEP, hits "
+                      "!= events, scratch_bytes >= pm_hip_flow_seq_rules_scratch_bytes)");
+        return -2;
+    }
+    if (!o->flow_seq_rules.nrules) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "pm_hip_set_flow_seq_rules was not called: a flow ordered-rules call needs the rule tables");
+        return -12;
+    }
+    if (nseg == 0) return 0;
+    hipError_t e = hipSetDevice(o->device);
+    serve_stop(o);  // a device launch wants the whole device
+    if (e == hipSuccess) {
+        if (cap == 0)
+            e = hipMemsetAsync(d_rule_ptr, 0, ((size_t)nseg + 1) * sizeof(int64_t), (hipStream_t)hip_stream);
+        else
+            e = pm_launch_flow_seq_rules(d_events, cap, d_nevents, d_offsets, nseg, o->flow_seq_rules, d_prog, nrows,
+                                         d_rows, d_pos_in, (flags & PM_FR_KEEP) != 0, d_hits, hits_cap, d_rule_ptr,
+                                         d_scratch, o->num_cu, (hipStream_t)hip_stream);
+    }
+    if (e != hipSuccess) {
+        std::snprintf(g_err, sizeof(g_err), "flow ordered rules launch: %s", hipGetErrorString(e));
+        return -3;
+    }
+    return 0;
+}
+
+// The host form, as pm_hip_flow_rules and on its staging (the rows in its
+// sets' array, the byte counts in the window call's): the committing call runs
+// exactly once; where the staging's hits array may be too short (it holds
+// fewer than the bound min(streams x rules, events x the most rules a gid
+// indexes)), a PM_FLOW_RULES_KEEP call counts them first and the array is
+// grown to the exact count.  Each stream's range is sorted here.
+int pm_hip_flow_seq_rules(void* obj, const uint64_t* events, size_t nevents, const int64_t* offsets, size_t nseg,
+                          uint64_t* prog, size_t nrows, const int64_t* rows, const uint64_t* pos_in, uint32_t flags,
+                          uint64_t* hits, size_t hits_cap, int64_t* rule_ptr) {
+    PmHip* o = as(obj);
+    if (!o->compiled) { std::snprintf(g_err, sizeof(g_err), "not compiled"); return -1; }
+    const uint64_t S = o->flow_seq_rules.words ? o->flow_seq_rules.words : 1;
+    if ((nevents && !events) || (nseg && (!offsets || !rule_ptr)) || !pos_in || (hits_cap && !hits) ||
+        nseg >= (size_t)PM_BS_MAX_NSEG || nevents > PM_BS_MAX_CAP || (hits && hits == events) ||
+        (flags & ~PM_FR_KEEP) || (nrows && !prog) || nrows > PM_FR_MAX_WORDS / S || (!rows && nrows < nseg)) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "bad arguments (events, offsets, prog, pos_in, hits and rule_ptr non-NULL, nseg < 2^31, nevents "
+                      "<= 2^40, nrows x words <= 2^40, nrows >= nseg without rows, no flag but PM_FLOW_RULES_KEEP, "
+                      "hits != events)");
+        return -2;
+    }
+    if (!o->flow_seq_rules.nrules) {
+        std::snprintf(g_err, sizeof(g_err),
+                      "pm_hip_set_flow_seq_rules was not called: a flow ordered-rules call needs the rule tables");
+        return -12;
+    }
+    if (nseg == 0) return 0;
+    if (nevents == 0) {
+        std::fill(rule_ptr, rule_ptr + nseg + 1, (int64_t)0);
+        return 0;
+    }
+    PM_CHECK(hipSetDevice(o->device));
+    BatchStage& q = o->batch;
+    const size_t nwords = nrows * (size_t)S;
+    batch_stage_grow(q, 0, nseg);  // the stream and the offsets
+    stage_grow((void**)&q.d_bs_in, (void**)&q.d_bs_out, sizeof(uint64_t), q.cap_bs, nevents);
+    stage_grow((void**)&q.d_bs_ptr, nullptr, sizeof(int64_t), q.cap_bs_ptr, nseg + 2);  // + the list's cursor
+    stage_grow(&q.d_bs_scr, nullptr, 1, q.cap_bs_scr, pm_seq_rules_layout(nevents, (int64_t)nseg).bytes);
+    stage_grow((void**)&q.d_rl_hits, nullptr, sizeof(uint64_t), q.cap_rl_hits, nevents);
+    stage_grow((void**)&q.d_fr_sets, nullptr, sizeof(uint64_t), q.cap_fr_sets, std::max(nwords, (size_t)1));
+    stage_grow((void**)&q.d_pos_in, (void**)&q.d_pos_out, sizeof(uint64_t), q.cap_pos, nseg);
+    if (rows) stage_grow((void**)&q.d_fr_rows, nullptr, sizeof(int64_t), q.cap_fr_rows, nseg);
+    unsigned long long* d_cursor = reinterpret_cast<unsigned long long*>(q.d_bs_ptr + nseg + 1);
+    const unsigned long long cursor = nevents;
+    serve_stop(o);  // a device launch wants the whole device
+    PM_CHECK(hipMemcpyAsync(q.d_bs_in, events, nevents * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(q.d_offs, offsets, (nseg + 1) * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(d_cursor, &cursor, sizeof(cursor), hipMemcpyHostToDevice, q.s));
+    PM_CHECK(hipMemcpyAsync(q.d_pos_in, pos_in, nseg * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    if (nwords) PM_CHECK(hipMemcpyAsync(q.d_fr_sets, prog, nwords * sizeof(uint64_t), hipMemcpyHostToDevice, q.s));
+    if (rows) PM_CHECK(hipMemcpyAsync(q.d_fr_rows, rows, nseg * sizeof(int64_t), hipMemcpyHostToDevice, q.s));
+    std::vector<int64_t> ptr(nseg + 1);
+    const bool keep = (flags & PM_FR_KEEP) != 0;
+    const uint64_t by_rules = (uint64_t)nseg * o->flow_seq_rules.nrules,
+                   by_events = (uint64_t)nevents * o->flow_seq_rules_fanout;
+    bool dry = q.cap_rl_hits < std::min(by_rules, by_events);  // the hits may not fit: count them first
+    for (;;) {
+        const hipError_t e = pm_launch_flow_seq_rules(q.d_bs_in, nevents, d_cursor, q.d_offs, (int64_t)nseg,
+                                                      o->flow_seq_rules, q.d_fr_sets, (int64_t)nrows,
+                                                      rows ? q.d_fr_rows : nullptr, q.d_pos_in, keep || dry,
+                                                      q.d_rl_hits, q.cap_rl_hits, q.d_bs_ptr, q.d_bs_scr, o->num_cu, q.s);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(q.s);
+            std::snprintf(g_err, sizeof(g_err), "flow ordered rules launch: %s", hipGetErrorString(e));
+            return -3;
+        }
+        PM_CHECK(hipMemcpyAsync(ptr.data(), q.d_bs_ptr, ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, q.s));
+        PM_CHECK(hipStreamSynchronize(q.s));
+        if (!dry) break;
+        dry = false;
+        if ((size_t)ptr[nseg] <= q.cap_rl_hits && keep) break;  // the dry call was the call asked for
+        stage_grow((void**)&q.d_rl_hits, nullptr, sizeof(uint64_t), q.cap_rl_hits, (size_t)ptr[nseg]);
+    }
+    const size_t total = (size_t)ptr[nseg];
+    std::vector<uint64_t> hv(total);
+    if (total) PM_CHECK(hipMemcpyAsync(hv.data(), q.d_rl_hits, total * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
+    if (nwords && !keep)
+        PM_CHECK(hipMemcpyAsync(prog, q.d_fr_sets, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost, q.s));
     PM_CHECK(hipStreamSynchronize(q.s));
     par_range(nseg, (size_t)1 << 12, [&](size_t lo, size_t hi) {
         for (size_t j = lo; j < hi; ++j) std::sort(hv.begin() + ptr[j], hv.begin() + ptr[j + 1]);

@@ -121,6 +121,11 @@ hipError_t pm_launch_seq_rules_by_stream(const uint64_t* events, uint64_t cap, c
                                          const int64_t* offsets, int64_t nseg, const PmSeqRulesDev& rules,
                                          uint64_t* hits, uint64_t hits_cap, int64_t* rule_ptr, void* scratch, int num_cu,
                                          hipStream_t s);
+// The index alone (the fills and passes 1 to 4, under the same conditions): on
+// return the stream holds the frozen table, the slots' ranges and the sorted
+// positions in scratch, and cnt is zeroed for the caller's own evaluation.
+hipError_t pm_launch_seq_index(const uint64_t* events, uint64_t cap, const unsigned long long* nevents,
+                               const int64_t* offsets, int64_t nseg, void* scratch, int num_cu, hipStream_t s);
 #endif
 
 #endif  // PM_SEQRULES_H

@@ -473,6 +473,44 @@ sq_eval_within_kernel(const u64* __restrict__ keys, const int64_t* __restrict__ 
 
 }  // namespace
 
+// The index alone, for a caller with an evaluation of its own
+// (pm_flowseqrules.hip): the fills and passes 1 to 4 of the launcher below, which
+// keeps its own copy of them: the two are to be kept in step.
+hipError_t pm_launch_seq_index(const uint64_t* events, uint64_t cap, const unsigned long long* nevents,
+                               const int64_t* offsets, int64_t nseg, void* scratch, int num_cu, hipStream_t s) {
+    const PmSeqRulesLayout l = pm_seq_rules_layout(cap, nseg);
+    char* base = (char*)scratch;
+    u64* keys = (u64*)(base + l.keys_off);
+    u64* pos = (u64*)(base + l.pos_off);
+    u64* scnt = (u64*)(base + l.scnt_off);
+    int64_t* start = (int64_t*)(base + l.start_off);
+    u64* occ = (u64*)(base + l.occ_off);
+    uint32_t* wl = (uint32_t*)(base + l.wl_off);
+    uint32_t* wlcur = (uint32_t*)(base + l.wlcur_off);
+    u64* sbsum = (u64*)(base + l.sbsum_off);
+    u64* cnt = (u64*)(base + l.cnt_off);
+    hipError_t e = hipMemsetAsync(keys, 0xFF, 2 * (size_t)l.table * sizeof(u64), s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(scnt, 0, (size_t)l.table * sizeof(u64), s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(wlcur, 0, 16, s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(cnt, 0, (size_t)nseg * sizeof(u64), s);
+    if (e != hipSuccess) return e;
+    int shift = 64;
+    for (uint64_t t = l.table; t > 1; t >>= 1) --shift;
+    const int egrid = pm_bs_grid(cap, num_cu), tgrid = pm_bs_grid(l.table, num_cu);
+    sq_insert_kernel<<<egrid, BS_THREADS, 0, s>>>(events, cap, nevents, offsets, nseg, keys, pos, scnt, l.table - 1,
+                                                   shift, l.table);
+    pm_launch_bs_scan(scnt, (int64_t)l.table, sbsum, start, s);
+    sq_scatter_kernel<<<egrid, BS_THREADS, 0, s>>>(events, cap, nevents, offsets, nseg, keys, scnt, start, occ,
+                                                    l.table - 1, shift, l.table);
+    sq_sort_short_kernel<<<tgrid, BS_THREADS, 0, s>>>(keys, start, occ, l.table, cap, wl, wlcur, l.wl_cap);
+    sq_sort_long_kernel<<<pm_bs_grid(l.wl_cap * BS_THREADS, num_cu), BS_THREADS, 0, s>>>(start, occ, l.table, cap, wl,
+                                                                                         wlcur, l.wl_cap);
+    return hipGetLastError();
+}
+
 hipError_t pm_launch_seq_rules_by_stream(const uint64_t* events, uint64_t cap, const unsigned long long* nevents,
                                          const int64_t* offsets, int64_t nseg, const PmSeqRulesDev& rules,
                                          uint64_t* hits, uint64_t hits_cap, int64_t* rule_ptr, void* scratch, int num_cu,
@@ -489,6 +527,7 @@ hipError_t pm_launch_seq_rules_by_stream(const uint64_t* events, uint64_t cap, c
     u64* sbsum = (u64*)(base + l.sbsum_off);
     u64* cnt = (u64*)(base + l.cnt_off);
     u64* bsum = (u64*)(base + l.bsum_off);
+    // the fills and passes 1 to 4 below are also pm_launch_seq_index's, above: a change to the index goes into both
     // keys and pos lie back to back: one fill empties both
     hipError_t e = hipMemsetAsync(keys, 0xFF, 2 * (size_t)l.table * sizeof(u64), s);
     if (e != hipSuccess) return e;

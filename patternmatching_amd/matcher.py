@@ -410,6 +410,75 @@ def flow_rules_host(events, offsets, rules, sets, rows=None, keep=False):
     return ptr, hits[:int(ptr[-1])]
 
 
+def _packed_flow_seq(rules, fast=None):
+    """(term_ptr, terms, gaps) of flow ordered rules in the packed form or as
+    any sequence of rules; a within is an error."""
+    ptr, terms, gaps, withins = _packed_seq(rules, fast)
+    if withins is not None and np.any(withins != SEQ_FREE):
+        raise ValueError("flow ordered rules take no within: a bound across packets is out of scope")
+    return ptr, terms, gaps
+
+
+def _flow_seq_host_args(offsets, prog, rows, pos_in):
+    offs, prog, rows, ptr = _flow_rules_host_args(offsets, prog, rows)
+    pos_in = np.ascontiguousarray(pos_in, dtype=np.uint64)
+    if pos_in.shape != (offs.size - 1,):
+        raise ValueError("pos_in: the bytes each flow had before the call, one per stream")
+    return offs, prog, rows, pos_in, ptr
+
+
+def flow_seq_rule_layout_host(rules, pattern_len):
+    """pm_flat_flow_seq_rule_layout: (chain_word u32 by term with 0xFFFFFFFF
+    where the term heads no chain of two or more, bit_by_gid u32 of npat + 1
+    with 0xFFFFFFFF for a gid without a bit, C, K, S): the layout of a flow's
+    progress row.  rules as pack_seq_rules takes them, or its triple."""
+    tptr, terms, gaps = _packed_flow_seq(rules)
+    plen = np.ascontiguousarray(pattern_len, dtype=np.uint32)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    chain = np.zeros(max(len(terms), 1), dtype=np.uint32)
+    bits = np.zeros(len(plen), dtype=np.uint32)
+    c, k, s = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    rc = load().pm_flat_flow_seq_rule_layout(tptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
+                                             gaps.ctypes.data_as(u32p), len(tptr) - 1, plen.ctypes.data_as(u32p),
+                                             len(plen) - 1, chain.ctypes.data_as(u32p), bits.ctypes.data_as(u32p),
+                                             ctypes.byref(c), ctypes.byref(k), ctypes.byref(s))
+    if rc != 0:
+        raise ValueError(f"pm_flat_flow_seq_rule_layout: bad arguments ({rc})")
+    return chain[:len(terms)], bits, int(c.value), int(k.value), int(s.value)
+
+
+def flow_seq_rules_host(events, offsets, rules, pattern_len, prog, pos_in, rows=None, keep=False):
+    """pm_flat_flow_seq_rules, the host twin of HipMatcher.flow_seq_rules (no
+    matcher, no device): (rule_ptr int64 of nseg + 1, hits u64 of position <<
+    24 | rule) with each stream's range ascending: the ordered rules (distance
+    only) that became true in this call's bytes, given each flow's progress in
+    its row of prog ((nrows, S) u64, flow_seq_rule_layout_host's S) and the
+    bytes pos_in[j] that flow j had before the call.  rows[j] is the row of
+    stream j (None: row j).  prog is updated in place unless keep.  rules as
+    pack_seq_rules takes them, or its triple; pattern_len by gid ([0] == 0)."""
+    ev = np.ascontiguousarray(events, dtype=np.uint64).ravel()
+    offs, prog, rows, pos_in, ptr = _flow_seq_host_args(offsets, prog, rows, pos_in)
+    tptr, terms, gaps = _packed_flow_seq(rules)
+    plen = np.ascontiguousarray(pattern_len, dtype=np.uint32)
+    u64p, i64p, u32p = (ctypes.POINTER(t) for t in (ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32))
+
+    def call(flags, hits):
+        rc = load().pm_flat_flow_seq_rules(ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p), offs.size - 1,
+                                           tptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
+                                           gaps.ctypes.data_as(u32p), len(tptr) - 1, plen.ctypes.data_as(u32p),
+                                           len(plen) - 1, prog.ctypes.data_as(u64p), prog.shape[0], prog.shape[1],
+                                           None if rows is None else rows.ctypes.data_as(i64p),
+                                           pos_in.ctypes.data_as(u64p), flags, hits.ctypes.data_as(u64p), len(hits),
+                                           ptr.ctypes.data_as(i64p))
+        if rc != 0:
+            raise ValueError(f"pm_flat_flow_seq_rules: bad arguments ({rc})")
+    # the hits are not bounded by the events and a committing call cannot be repeated: count them first
+    call(FLOW_RULES_KEEP, np.empty(0, dtype=np.uint64))
+    hits = np.empty(int(ptr[-1]), dtype=np.uint64)
+    call(FLOW_RULES_KEEP if keep else 0, hits)
+    return ptr, hits[:int(ptr[-1])]
+
+
 class FlowTable:
     """The carried states of many live flows over one matcher (ac / auto
     kinds): a dict of flow key -> flow state, and one flow call
@@ -429,7 +498,12 @@ class FlowTable:
     For it the table keeps each flow's set of carried terms (rule_sets: W u64
     words per flow, HipMatcher.flow_rule_words) and the bytes the flow had
     when scan_rules() last saw it (rule_bytes).  A flow is followed by
-    scan_rules() from its first byte or not at all."""
+    scan_rules() from its first byte or not at all.
+
+    scan_seq_rules() does the same for the flow ordered rules
+    (HipMatcher.set_flow_seq_rules): it keeps each flow's progress row
+    (seq_rule_rows: flow_seq_rule_words u64 per flow) and the bytes the flow
+    had when it last saw it (seq_rule_bytes)."""
 
     def __init__(self, matcher):
         self.matcher = matcher
@@ -438,6 +512,9 @@ class FlowTable:
         # scan_rules: the carried terms of each flow, and the bytes it saw
         self.rule_sets = {}
         self.rule_bytes = {}
+        # scan_seq_rules: the progress row of each flow, and the bytes it saw
+        self.seq_rule_rows = {}
+        self.seq_rule_bytes = {}
         # scan_nocase: the folded automaton's states, the case histories, and the bytes it saw
         self.nocase_states = {}
         self.nocase_case = {}
@@ -582,6 +659,53 @@ class FlowTable:
         hpos, rule = unpack_events(hits)
         return [(hpos[ptr[j]:ptr[j + 1]] - offs[j], rule[ptr[j]:ptr[j + 1]]) for j in range(len(packets))]
 
+    def scan_seq_rules(self, packets):
+        """scan_rules() for the flow ordered rules
+        (HipMatcher.set_flow_seq_rules): per packet, in order, (positions
+        inside the packet, rule indices) of the ordered rules that became
+        true in that packet, ascending by (position, rule): a chain's head
+        may lie in an earlier packet than its follower, and a link is
+        measured in the flow's bytes.  One read_flows_matches call at
+        flow_seq_rules_min_len() from the flows' states, then flow_seq_rules
+        over the flows' kept rows and the table's byte counts.  The flows'
+        states and byte counts advance exactly as in scan().  A flow that got
+        bytes through another scan method since scan_seq_rules() last saw it
+        cannot be continued (its row missed their patterns): ValueError; so
+        is a kept row whose length is not the matcher's current
+        flow_seq_rule_words (the rules were replaced)."""
+        keys = [k for k, _ in packets]
+        _unique_keys(keys, "scan_seq_rules")
+        S = self.matcher.flow_seq_rule_words
+        if S == 0:
+            raise ValueError("scan_seq_rules() before the matcher's set_flow_seq_rules()")
+        for k in keys:
+            if self.bytes.get(k, 0) != self.seq_rule_bytes.get(k, 0):
+                raise ValueError(f"flow {k!r} has had {self.bytes.get(k, 0)} bytes but scan_seq_rules() saw "
+                                 f"{self.seq_rule_bytes.get(k, 0)} of them")
+            if k in self.seq_rule_rows and len(self.seq_rule_rows[k]) != S:
+                raise ValueError(f"flow {k!r} keeps a row of {len(self.seq_rule_rows[k])} words but the matcher's "
+                                 f"flow ordered rules need {S}")
+        if not packets:
+            return []
+        data, offs = _concat([b for _, b in packets])
+        state = np.array([self.states.get(k, 0) for k in keys], dtype=np.uint32)
+        pos_in = np.array([self.bytes.get(k, 0) for k in keys], dtype=np.uint64)
+        prog = np.zeros((len(keys), S), dtype=np.uint64)
+        for r, k in enumerate(keys):
+            if k in self.seq_rule_rows:
+                prog[r] = self.seq_rule_rows[k]
+        ev, state = self.matcher._read_events(data, offs, state, self.matcher.flow_seq_rules_min_len(),
+                                              all_matches=True)
+        ptr, hits = self.matcher.flow_seq_rules(ev, offs, prog, pos_in)
+        for r, (k, s) in enumerate(zip(keys, state.tolist())):
+            self.states[k] = s
+            self.seq_rule_rows[k] = prog[r].copy()
+        self._advance(keys, offs)
+        for k in keys:
+            self.seq_rule_bytes[k] = self.bytes[k]
+        hpos, rule = unpack_events(hits)
+        return [(hpos[ptr[j]:ptr[j + 1]] - offs[j], rule[ptr[j]:ptr[j + 1]]) for j in range(len(packets))]
+
     def _advance(self, keys, offs):
         for k, n in zip(keys, np.diff(offs).tolist()):
             self.bytes[k] = self.bytes.get(k, 0) + n
@@ -608,6 +732,8 @@ class FlowTable:
         self.nocase_bytes.pop(key, None)
         self.rule_sets.pop(key, None)
         self.rule_bytes.pop(key, None)
+        self.seq_rule_rows.pop(key, None)
+        self.seq_rule_bytes.pop(key, None)
 
     def __len__(self):
         return len(self.states)
@@ -1227,6 +1353,100 @@ class HipMatcher:
                                                    offs.size - 1, sets.ctypes.data_as(u64p), sets.shape[0],
                                                    None if rows is None else rows.ctypes.data_as(i64p), flags,
                                                    hits.ctypes.data_as(u64p), len(hits), ptr.ctypes.data_as(i64p)))
+        # the hits are not bounded by the events and a committing call cannot be repeated: count them first
+        call(FLOW_RULES_KEEP, np.empty(0, dtype=np.uint64))
+        hits = np.empty(int(ptr[-1]), dtype=np.uint64)
+        call(FLOW_RULES_KEEP if keep else 0, hits)
+        return ptr, hits[:int(ptr[-1])]
+
+    # --- flow ordered rules: each chain's progress per flow, carried from call to call ---
+    def set_flow_seq_rules(self, rules, fast=None):
+        """pm_hip_set_flow_seq_rules: a rule set of its own for
+        flow_seq_rules(), in pack_seq_rules' term forms (the other three rule
+        sets are not touched).  A term with a within raises ValueError: a
+        bound across packets is out of scope.  fast is accepted and has no
+        effect on the results.  After compile(); a later call replaces the
+        set, and with it the layout of a flow's row."""
+        ptr, terms, gaps = _packed_flow_seq(rules, fast)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self.lib.pm_hip_set_flow_seq_rules(self.obj, ptr.ctypes.data_as(u32p), terms.ctypes.data_as(u32p),
+                                                       gaps.ctypes.data_as(u32p), len(ptr) - 1))
+
+    def flow_seq_rule_count(self):
+        """pm_hip_flow_seq_rule_count: the rules set (0 before set_flow_seq_rules)."""
+        return int(self.lib.pm_hip_flow_seq_rule_count(self.obj))
+
+    def flow_seq_rules_min_len(self):
+        """pm_hip_flow_seq_rules_min_len: the length of the shortest pattern
+        any term names (0 before set_flow_seq_rules)."""
+        return int(self.lib.pm_hip_flow_seq_rules_min_len(self.obj))
+
+    @property
+    def flow_seq_rule_words(self):
+        """pm_hip_flow_seq_rule_words: S, the u64 words of one flow's
+        progress row (0 before set_flow_seq_rules)."""
+        return int(self.lib.pm_hip_flow_seq_rule_words(self.obj))
+
+    def flow_seq_chain_count(self):
+        """pm_hip_flow_seq_chain_count: C, the chains of two or more positive
+        terms: the chain words at the front of a row."""
+        return int(self.lib.pm_hip_flow_seq_chain_count(self.obj))
+
+    def flow_seq_chain_word(self, rule, term_index):
+        """pm_hip_flow_seq_chain_word: the word of the chain headed by term
+        term_index of rule, as the rule was given, or -1."""
+        return int(self.lib.pm_hip_flow_seq_chain_word(self.obj, int(rule), int(term_index)))
+
+    def flow_seq_rule_bit(self, gid):
+        """pm_hip_flow_seq_rule_bit: the bit of gid (in word C + bit // 64, at
+        bit % 64), or -1 where it has none."""
+        return int(self.lib.pm_hip_flow_seq_rule_bit(self.obj, int(gid)))
+
+    def flow_seq_rules_scratch_bytes(self, cap, nseg):
+        """pm_hip_flow_seq_rules_scratch_bytes: the device scratch, in bytes,
+        that flow_seq_rules_device needs for a list of cap slots over nseg
+        streams."""
+        b = self.lib.pm_hip_flow_seq_rules_scratch_bytes(cap, nseg)
+        if b == ctypes.c_size_t(-1).value:
+            raise ValueError("flow_seq_rules_scratch_bytes: cap <= 2^40, 0 <= nseg < 2^31")
+        return b
+
+    def flow_seq_rules_device(self, d_events_ptr, cap, d_nevents_ptr, d_offsets_ptr, nseg, d_prog_ptr, nrows,
+                              d_rows_ptr, d_pos_in_ptr, flags, d_hits_ptr, hits_cap, d_rule_ptr_ptr, d_scratch_ptr,
+                              scratch_bytes, stream_ptr):
+        """pm_hip_flow_seq_rules_device: behind a flow scan's list (the
+        arguments of flow_rules_device), the ordered rules that became true
+        in this call's bytes, given each flow's row of the nrows x
+        flow_seq_rule_words u64 at d_prog_ptr and the nseg u64 byte counts at
+        d_pos_in_ptr that the flows had before the call; then the rows are
+        advanced, unless flags holds FLOW_RULES_KEEP.  Enqueued on
+        stream_ptr, no synchronize."""
+        rc = self.lib.pm_hip_flow_seq_rules_device(self.obj, d_events_ptr, cap, d_nevents_ptr, d_offsets_ptr, nseg,
+                                                   d_prog_ptr, nrows, d_rows_ptr, d_pos_in_ptr, flags, d_hits_ptr,
+                                                   hits_cap, d_rule_ptr_ptr, d_scratch_ptr, scratch_bytes, stream_ptr)
+        self._check(rc)
+
+    def flow_seq_rules(self, events, offsets, prog, pos_in, rows=None, keep=False):
+        """pm_hip_flow_seq_rules: host arrays through the device call:
+        (rule_ptr int64 of nseg + 1, hits u64), stream j's hits
+        hits[ptr[j]:ptr[j+1]] ascending, each position << 24 | rule.  prog is
+        a C-contiguous (nrows, flow_seq_rule_words) u64 array, a row per flow,
+        updated in place unless keep; pos_in[j] the bytes flow j had before
+        the call; rows[j] the row of stream j (None: row j).  events come from
+        an all-matches flow scan that continued the same flows, at a min_len
+        <= flow_seq_rules_min_len(), with a cap that held the list."""
+        ev = np.ascontiguousarray(events, dtype=np.uint64).ravel()
+        offs, prog, rows, pos_in, ptr = _flow_seq_host_args(offsets, prog, rows, pos_in)
+        u64p, i64p = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int64)
+        S = self.flow_seq_rule_words
+        if S and prog.shape[1] != S:  # (0: the call says what is missing)
+            raise ValueError(f"prog: {S} words per row, not {prog.shape[1]}")
+
+        def call(flags, hits):
+            self._check(self.lib.pm_hip_flow_seq_rules(
+                self.obj, ev.ctypes.data_as(u64p), len(ev), offs.ctypes.data_as(i64p), offs.size - 1,
+                prog.ctypes.data_as(u64p), prog.shape[0], None if rows is None else rows.ctypes.data_as(i64p),
+                pos_in.ctypes.data_as(u64p), flags, hits.ctypes.data_as(u64p), len(hits), ptr.ctypes.data_as(i64p)))
         # the hits are not bounded by the events and a committing call cannot be repeated: count them first
         call(FLOW_RULES_KEEP, np.empty(0, dtype=np.uint64))
         hits = np.empty(int(ptr[-1]), dtype=np.uint64)
